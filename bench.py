@@ -9,6 +9,8 @@ all on the device, then ONE RCCL all-gather of the rank's 32-byte result rows wh
 The one-time eigendecomposition of K is timed separately (`eigh_seconds`), as the metric asks.
 
     python bench.py                              # 1 GPU
+    python bench.py --dump-outputs DIR           # + the last timed step's result columns as DIR/<column>.npy (seeded inputs:
+                                                 #   two builds compare output for output)
     python bench.py --gpus N                     # spawns N ranks itself (one process per GPU), or run under any launcher:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
 
@@ -89,6 +91,27 @@ def geno_codes(rng, n, p, chunk=8192):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, host_rows, P, world):
+    """--dump-outputs: the columns lmm.pygemma would hand its caller (dist.unpack_gathered of the step's 32-byte result rows,
+    SNP order), one DIR/<column>.npy each.  Above DUMP_MAX_BYTES a fixed seeded sample of SNPs is written instead, and its
+    SNP indices as DIR/snp_index.npy (float64: exact)."""
+    from pygemma_amd import dist
+    cols = dist.unpack_gathered(host_rows, P * world, world)
+    total = P * world
+    per_snp = sum(v.dtype.itemsize for v in cols.values())
+    if total * per_snp > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 4096) // (per_snp + 8)         # 4 kB: the .npy headers
+        idx = np.sort(np.random.default_rng(12345).choice(total, keep, replace=False))
+        cols = {k: v[idx] for k, v in cols.items()}
+        cols["snp_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` without a launcher: start N child processes (one per GPU) BEFORE anything touches HIP in this
     process, hand them RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*, pass rank 0's JSON line through, return the worst exit code."""
@@ -143,7 +166,11 @@ def main():
     ap.add_argument("--e2e", type=int, default=1, help="1 = after the timed region also run lmm.pygemma from host X (incl. H2D and eigh)")
     ap.add_argument("--eigh-cache", default="", help="npz path: reuse U, d (and K-derived inputs) from a previous run instead of running "
                                                      "the eigensolver (rocprofv3 --pmc passes on the per-SNP kernels)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the six result columns of the last timed step as DIR/<column>.npy (a seeded sample of SNPs above 64 MB)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         raise SystemExit(spawn_ranks(a))        # nothing in this process has touched the GPU
@@ -310,6 +337,8 @@ def main():
             L.pg_event_elapsed_ms(ctx.handle, evs[bi][0], evs[bi][1], C.byref(ms)); rot_ms.append(ms.value)
             L.pg_event_elapsed_ms(ctx.handle, evs[bi][1], evs[bi][2], C.byref(ms)); assoc_ms.append(ms.value)
     stats = dstats.download((2,), np.uint64).astype(np.float64) / (P * a.steps)
+    if a.dump_outputs and rank == 0:       # before the report's extra passes overwrite `res`
+        dump_outputs(a.dump_outputs, (allres if comm is not None else res).download((32 * P * world,), np.uint8), P, world)
 
     if rank != 0:
         if comm is not None:
