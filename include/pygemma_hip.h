@@ -136,6 +136,21 @@ int pg_assoc_set_eval_trace(pg_ctx *ctx, unsigned *trace_dev);
  * still on the host link.  No reference counterpart: the reference has no device. */
 int pg_assoc_warm(pg_ctx *ctx, int64_t n, int c);
 
+/* Several phenotypes over one SNP block (the reference's callers loop lmm.pygemma over phenotype columns with the same X, W, K:
+ * experiments/wtccc/run_pygemma_imputed.py:516-532, experiments/animal_gwas/run_gwas.py:167-175).  For every phenotype k the six
+ * outputs are bit-identical to pg_assoc_dev(..., yr = Yr + k ldy, ...): the decade scan's Gram entries that do not involve y (x'HW,
+ * x'Hx at the 11 decade lambdas) are accumulated once per SNP for a chunk of up to 8 phenotypes, x'Hy_k once per phenotype, in the
+ * per-element order of pg_assoc_dev's scan; the lambda search then runs one wavefront per (SNP, phenotype).
+ *   Yr   t rotated phenotypes, phenotype-major: phenotype k is Yr[k ldy .. k ldy + n), ldy >= n
+ *   outputs: t x p, phenotype-major (phenotype k's SNP g at [k p + g]); pval may be NULL; stats as pg_assoc_dev (summed)
+ * Same argument checks as pg_assoc_dev, plus t >= 1 and ldy >= n. */
+int pg_assoc_pheno_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, int t, const float *d, const float *Wr,
+                       const float *Yr, int64_t ldy, const float *Xr, int64_t ldx, int grid,
+                       float *beta, float *se, float *tau, float *lambda, double *F, double *pval,
+                       unsigned long long *stats_dev);
+/* Optional, like pg_assoc_warm: the host-side set-up of a first pg_assoc_pheno_dev call with t phenotypes and up to p SNPs. */
+int pg_assoc_pheno_warm(pg_ctx *ctx, int64_t n, int c, int t, int64_t p);
+
 /* ---- N2: the same operator plus the likelihood-ratio test the reference sketches and leaves commented out
  * ("Fix these calculations later", lmm/lmm.py:137-141, 277-300), built from its own ML functions: lambda_alt =
  * calc_lambda(eigenVals, Y, [W, x]) (lmm/lmm.py:22-84: decade scan of dlogL/dlambda, brentq(rtol=0.1) + scipy newton),

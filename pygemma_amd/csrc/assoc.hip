@@ -56,6 +56,9 @@ constexpr int WPB = PG_ASSOC_WPB;
 #ifndef PG_SWEEP_LDS_MIN_SLOTS
 #define PG_SWEEP_LDS_MIN_SLOTS 3   // lanes owning this many Gram entries or more exchange the sweeps' pivot column through LDS
 #endif
+#ifndef PG_PHENO_SPLIT_XE
+#define PG_PHENO_SPLIT_XE 26   // multi-phenotype scan: rows of more entries (c + 1 + chunk width) accumulate P and Q in separate passes
+#endif
 #ifndef PG_WAVES
 #define PG_WAVES 2          // waves per SIMD the register allocation is held to
 #endif
@@ -89,6 +92,10 @@ struct AssocParams {
     int lrt, nhalf;
     float ml_c;
     float *lalt, *lamalt;
+    // pg_assoc_pheno_dev (PHENO instantiations only): the x-entries of the decade scan come from scan_pheno_kernel's buffer
+    // xbuf [p][NLAM][2][xe] (xe = c + 1 shared entries + the chunk's padded phenotype count); this launch's phenotype is column xcol
+    const double *xbuf;
+    int xe, xcol;
 };
 
 // quadratic forms of one evaluation; sh, shh = the level-0 (un-projected) traces sum h, sum h^2 the ML functions use
@@ -724,6 +731,105 @@ __device__ __forceinline__ void scan_all(const AssocParams &pr, const float *xro
     }
 }
 
+// Multi-phenotype decade scan (pg_assoc_pheno_dev): the x-entries of TC phenotypes at once.  P(x,k) and Q(x,k), k <= C, do not involve
+// y and are accumulated once; P(y_j,x), Q(y_j,x) once per phenotype j: C + 1 + TC values per lambda and power instead of TC (C + 2).
+// Every value is the per-lane fma chain of scan_accumulate (same products z, same element order) and goes through reduce_scatter,
+// whose additions do not depend on how the values are grouped: the totals are scan_accumulate's bits.  Phenotypes j >= tcn (the pad
+// of a chunk up to TC) read y = 0.  out: this SNP's [NLAM][2][XE] row of the scan buffer.  PWS powers per pass from PW0 (2, 0: P and Q;
+// 1, pw: one of them, for wide rows: the products z are then used once each and need not stay in registers).
+template <int C, int TC, int GG, int PWS, int PW0>
+__device__ __forceinline__ void scan_pheno_accumulate(const AssocParams &pr, const float *xrow, const float *Y, long long ldy, int tcn,
+                                                      int t0, int lane, double *out)
+{
+    constexpr int M = Shape<C>::M, XE = C + 1 + TC, NV = GG * PWS * XE;
+    // accumulator v -> lambda t0 + v / (PWS XE), power PW0 + (v % (PWS XE)) / XE, entry v % XE of the [NLAM][2][XE] row
+    auto dest = [&](int v) { const int gg = v / (PWS * XE), r = v - gg * PWS * XE; return (t0 + gg) * 2 * XE + PW0 * XE + r; };
+    constexpr int NV0 = NV < 64 ? NV : 64, NV1 = NV > 64 ? NV - 64 : 0;
+    constexpr int NVP0 = next_pow2(NV0), NVP1 = next_pow2(NV1 > 0 ? NV1 : 1);
+    static_assert(NV <= 128, "scan group too large");
+    double acc[NV0 == 64 ? 64 + NVP1 : NVP0];
+#pragma unroll
+    for (int k = 0; k < (NV0 == 64 ? 64 + NVP1 : NVP0); k++) acc[k] = 0.0;
+    struct SE { Elem<C> e; float y[TC]; float h[GG]; };
+    pipelined<SE>(pr.niter, [&](SE &q, int it) {
+        const int i = it * 64 + lane;
+        load_elem<C>(pr, xrow, i, q.e);
+#pragma unroll
+        for (int j = 0; j < TC; j++) q.y[j] = (i < pr.n && j < tcn) ? Y[(size_t)j * ldy + i] : 0.0f;   // pad rows: y = 0 as in the fixed rows
+#pragma unroll
+        for (int g = 0; g < GG; g++) q.h[g] = pr.htab[(size_t)(t0 + g) * pr.npad + i];
+    }, [&](const SE &q, int it) {
+        const int i = it * 64 + lane;
+        float d, colf[M];
+        unpack_elem<C>(pr, q.e, i, d, colf);
+        const double xd = (double)colf[C];
+        double z[XE];
+#pragma unroll
+        for (int k = 0; k <= C; k++) z[k] = xd * (double)colf[k];
+#pragma unroll
+        for (int j = 0; j < TC; j++) z[C + 1 + j] = (double)q.y[j] * xd;
+#pragma unroll
+        for (int g = 0; g < GG; g++) {
+            const double hd = (double)q.h[g];
+            const double h2 = hd * hd;
+#pragma unroll
+            for (int k = 0; k < XE; k++) {
+                if constexpr (PWS == 2) {
+                    acc[g * 2 * XE + k] = fma(hd, z[k], acc[g * 2 * XE + k]);
+                    acc[g * 2 * XE + XE + k] = fma(h2, z[k], acc[g * 2 * XE + XE + k]);
+                } else {
+                    acc[g * XE + k] = fma(PW0 == 0 ? hd : h2, z[k], acc[g * XE + k]);
+                }
+            }
+        }
+    });
+    {
+        double t[NVP0];
+#pragma unroll
+        for (int k = 0; k < NVP0; k++) t[k] = acc[k];
+        const double tot = reduce_scatter<NVP0>(t, lane);
+        const int idx = lane % NVP0;
+        if (idx < NV0 && lane < NVP0) out[dest(idx)] = tot;
+    }
+    if constexpr (NV1 > 0) {
+        double t[NVP1];
+#pragma unroll
+        for (int k = 0; k < NVP1; k++) t[k] = acc[64 + k];
+        const double tot = reduce_scatter<NVP1>(t, lane);
+        const int idx = lane % NVP1;
+        if (idx < NV1 && lane < NVP1) out[dest(64 + idx)] = tot;
+    }
+}
+template <int C, int TC, int T0>
+__device__ __forceinline__ void scan_pheno_all(const AssocParams &pr, const float *xrow, const float *Y, long long ldy, int tcn, int lane,
+                                               double *out)
+{
+    // lambdas per pass: the 2 XE accumulators of each plus the XE products z held across them within the SCAN_NV budget; rows wider
+    // than PG_PHENO_SPLIT_XE take one pass per power and lambda (the register report: from c = 23 on hundreds of VGPRs spilled otherwise)
+    constexpr int XE = C + 1 + TC, PWS = XE > PG_PHENO_SPLIT_XE ? 1 : 2;
+    constexpr int G0 = PWS == 1 ? 1 : (Shape<C>::SCAN_NV - XE) / (PWS * XE), G = G0 < 1 ? 1 : (G0 > NLAM ? NLAM : G0);
+    if constexpr (T0 < NLAM) {
+        constexpr int GG = (NLAM - T0) < G ? (NLAM - T0) : G;
+        if constexpr (PWS == 2) {
+            scan_pheno_accumulate<C, TC, GG, 2, 0>(pr, xrow, Y, ldy, tcn, T0, lane, out);
+        } else {
+            scan_pheno_accumulate<C, TC, GG, 1, 0>(pr, xrow, Y, ldy, tcn, T0, lane, out);
+            scan_pheno_accumulate<C, TC, GG, 1, 1>(pr, xrow, Y, ldy, tcn, T0, lane, out);
+        }
+        scan_pheno_all<C, TC, T0 + GG>(pr, xrow, Y, ldy, tcn, lane, out);
+    }
+}
+constexpr int SCAN_WPB = 4;   // SNPs (wavefronts) per workgroup of scan_pheno_kernel: no LDS, no barrier, no straggler
+// One wavefront per SNP: the rows [NLAM][2][C + 1 + TC] of xbuf for pr.p SNPs of pr.xr; Y: tcn rotated phenotypes, row stride ldy.
+template <int C, int TC>
+__global__ __launch_bounds__(64 * SCAN_WPB, PG_WAVES) void scan_pheno_kernel(AssocParams pr, const float *Y, long long ldy, int tcn, double *xbuf)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long g = (long long)blockIdx.x * SCAN_WPB + wave;
+    if (g >= pr.p) return;
+    scan_pheno_all<C, TC, 0>(pr, pr.xr + (size_t)g * pr.ldx, Y, ldy, tcn, lane, xbuf + (size_t)g * NLAM * 2 * (C + 1 + TC));
+}
+
 __device__ __forceinline__ void wave_lds_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -801,7 +907,9 @@ __device__ __forceinline__ float newton_dev(const AssocParams &pr, float lroot, 
     return lroot;
 }
 
-template <int C, bool LRT>
+template <int C, bool LRT, bool PHENO = false>
+// PHENO (pg_assoc_pheno_dev; never with LRT): the decade scan's x-entries are read from pr.xbuf; one launch per phenotype, so that
+// every (SNP, phenotype) is one wavefront and a workgroup holds WPB of them, as in a single-phenotype launch.
 // two waves per SIMD for EVERY c (PG_WAVES = 2): a lone wave cannot issue fp64 VALU at the pipe's rate (measured 2.3x faster at 2 than at
 // 1).  From c = 4 on the instantiations are capped at 256 VGPRs with spills to scratch (c = 5: 58 VGPR + 35 SGPR spills, 196 B; c = 10:
 // 107, 320 B; c = 14: 276 B) — all of them in the per-evaluation outer loops; the Gram loops themselves are scratch-free (checked on the
@@ -811,6 +919,7 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
     constexpr int M = Shape<C>::M, NP = Shape<C>::NP, SLOTS = Shape<C>::SLOTS;
     extern __shared__ unsigned char smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    static_assert(!(PHENO && LRT), "the multi-phenotype search has no LRT");
     const long long g = (long long)blockIdx.x * WPB + wave;
     if (g >= pr.p) return;  // whole wavefront leaves; no workgroup barrier is used anywhere in this kernel
     // per-wave LDS: xent[NLAM][2M] doubles | evs[NLAM] | d1s[NLAM] | lls[NLAM] | vals[n_vals]
@@ -828,7 +937,15 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
     Own<C> own;
     own.init(lane);
     // ---- decade scan: x-dependent Gram entries at the 11 shared lambdas
-    scan_all<C, 0>(pr, xrow, lane, xent);
+    if constexpr (PHENO) {   // from the scan buffer: xent[t][pw][k] = row (t, pw) entry k (k <= C) or this phenotype's (k = C + 1)
+        const double *src = pr.xbuf + (size_t)g * NLAM * 2 * pr.xe;
+        for (int j = lane; j < NLAM * 2 * M; j += 64) {
+            const int tp = j / M, k = j - tp * M;
+            xent[j] = src[(size_t)tp * pr.xe + (k <= C ? k : pr.xcol)];
+        }
+    } else {
+        scan_all<C, 0>(pr, xrow, lane, xent);
+    }
     wave_lds_sync();
     for (int t = 0; t < NLAM; t++) {
         double P[SLOTS], Q[SLOTS], R[SLOTS];
@@ -971,6 +1088,42 @@ static int launch_assoc(pg_ctx *ctx, AssocParams &pr)
     return PG_OK;
 }
 
+// The kernels of pg_assoc_pheno_dev, one launch per call: SETUP = setup_tabs_kernel for one phenotype (pr.fixed / pr.fixg are its own),
+// SCAN = scan_pheno_kernel over pr.p SNPs for a chunk of tcn phenotypes padded to tpad (1, 2, 4 or 8), SEARCH = the lambda search of
+// assoc_kernel for one phenotype (pr.fixed, pr.fixg, pr.xcol and the outputs are its own), one wavefront per SNP.
+struct PhenoLaunch {
+    enum { SETUP, SCAN, SEARCH } phase;
+    const float *Y; long long ldy;
+    int tcn, tpad;
+    double *xbuf;
+};
+constexpr int PHENO_CHUNK = 8;   // phenotypes per scan pass: C + 1 + 8 entries per lambda and power (47 at c = 30) keep 1 - 3 lambdas per pass
+template <int C>
+static int launch_pheno(pg_ctx *ctx, AssocParams &pr, const PhenoLaunch &pl)
+{
+    if (pl.phase == PhenoLaunch::SETUP) {
+        setup_tabs_kernel<C><<<NLAM, 64, (size_t)pr.n_vals * 4 + 16, ctx->stream>>>(pr);
+    } else if (pl.phase == PhenoLaunch::SCAN) {
+        const unsigned nblk = (unsigned)((pr.p + SCAN_WPB - 1) / SCAN_WPB);
+        switch (pl.tpad) {
+            case 1: scan_pheno_kernel<C, 1><<<nblk, 64 * SCAN_WPB, 0, ctx->stream>>>(pr, pl.Y, pl.ldy, pl.tcn, pl.xbuf); break;
+            case 2: scan_pheno_kernel<C, 2><<<nblk, 64 * SCAN_WPB, 0, ctx->stream>>>(pr, pl.Y, pl.ldy, pl.tcn, pl.xbuf); break;
+            case 4: scan_pheno_kernel<C, 4><<<nblk, 64 * SCAN_WPB, 0, ctx->stream>>>(pr, pl.Y, pl.ldy, pl.tcn, pl.xbuf); break;
+            case 8: scan_pheno_kernel<C, 8><<<nblk, 64 * SCAN_WPB, 0, ctx->stream>>>(pr, pl.Y, pl.ldy, pl.tcn, pl.xbuf); break;
+            default: set_error("assoc_pheno: chunk width %d", pl.tpad); return PG_EINVAL;
+        }
+    } else {
+        const size_t lds = (size_t)WPB * assoc_per_wave_bytes(Shape<C>::M, Shape<C>::SWEEP_LDS, sizeof(EvalOut), pr.n_vals);
+        PG_REQUIRE(pr.n_vals >= 0 && lds <= 160 * 1024, "assoc_pheno: c = %d, n_vals = %d need %zu bytes of LDS per workgroup", C, pr.n_vals, lds);
+        if (lds > 64 * 1024)
+            PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&assoc_kernel<C, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const long long nblk = (pr.p + WPB - 1) / WPB;
+        assoc_kernel<C, false, true><<<dim3((unsigned)nblk), 64 * WPB, lds, ctx->stream>>>(pr);
+    }
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
 
 // The association kernel is instantiated per covariate count (and once more with the LRT search, N2); the instantiations
 // are split over translation units so that they compile in parallel:
@@ -980,8 +1133,30 @@ static int launch_assoc(pg_ctx *ctx, AssocParams &pr)
 int launch_assoc_hi(pg_ctx *ctx, AssocParams &pr);
 int launch_assoc_lrt(pg_ctx *ctx, AssocParams &pr);
 int launch_assoc_lrt_hi(pg_ctx *ctx, AssocParams &pr);
+//   assoc_pheno.hip    multi-phenotype kernels (pg_assoc_pheno_dev), c = 1..15     assoc_pheno_hi.hip  c = 16..PG_MAX_COVARIATES
+int launch_assoc_pheno(pg_ctx *ctx, AssocParams &pr, const PhenoLaunch &pl);
+int launch_assoc_pheno_hi(pg_ctx *ctx, AssocParams &pr, const PhenoLaunch &pl);
 #define PG_CASE(CC) case CC: return launch_assoc<CC, PG_CASE_LRT>(ctx, pr);
-#if defined(PG_ASSOC_PART) && PG_ASSOC_PART == 1
+#define PG_PCASE(CC) case CC: return launch_pheno<CC>(ctx, pr, pl);
+#if defined(PG_ASSOC_PART) && PG_ASSOC_PART == 4
+int launch_assoc_pheno(pg_ctx *ctx, AssocParams &pr, const PhenoLaunch &pl)
+{
+    switch (pr.c) {
+        PG_PCASE(1) PG_PCASE(2) PG_PCASE(3) PG_PCASE(4) PG_PCASE(5) PG_PCASE(6) PG_PCASE(7) PG_PCASE(8) PG_PCASE(9) PG_PCASE(10)
+        PG_PCASE(11) PG_PCASE(12) PG_PCASE(13) PG_PCASE(14) PG_PCASE(15)
+        default: return launch_assoc_pheno_hi(ctx, pr, pl);
+    }
+}
+#elif defined(PG_ASSOC_PART) && PG_ASSOC_PART == 5
+int launch_assoc_pheno_hi(pg_ctx *ctx, AssocParams &pr, const PhenoLaunch &pl)
+{
+    switch (pr.c) {
+        PG_PCASE(16) PG_PCASE(17) PG_PCASE(18) PG_PCASE(19) PG_PCASE(20) PG_PCASE(21) PG_PCASE(22) PG_PCASE(23) PG_PCASE(24) PG_PCASE(25)
+        PG_PCASE(26) PG_PCASE(27) PG_PCASE(28) PG_PCASE(29) PG_PCASE(30)
+        default: return PG_ENOTSUP;
+    }
+}
+#elif defined(PG_ASSOC_PART) && PG_ASSOC_PART == 1
 #define PG_CASE_LRT false
 int launch_assoc_hi(pg_ctx *ctx, AssocParams &pr)
 {
@@ -1034,9 +1209,11 @@ int launch_assoc_lrt(pg_ctx *ctx, AssocParams &pr)
     switch (pr.c) { PG_CASE(PG_ONLY_C) case PG_ONLY_C - 1: return launch_assoc<PG_ONLY_C - 1, true>(ctx, pr); default: return PG_ENOTSUP; }
 }
 int launch_assoc_hi(pg_ctx *, AssocParams &) { return PG_ENOTSUP; }
+int launch_assoc_pheno(pg_ctx *, AssocParams &, const PhenoLaunch &) { return PG_ENOTSUP; }
 #endif
 #endif
 #undef PG_CASE
+#undef PG_PCASE
 
 #ifndef PG_ASSOC_PART
 // ------------------------------------------------------------------------------------------------
@@ -1314,6 +1491,28 @@ extern "C" int pg_transpose_dev(pg_ctx *ctx, int64_t n, int64_t p, const float *
     return PG_OK;
 }
 
+// the SNP-independent scalars of the kernel parameters (shapes, decade lambdas, likelihood constants, the float32-sum plan)
+static void fill_params(pg_ctx *ctx, int64_t n, int c, int grid, AssocParams &pr)
+{
+    pr.n = (int)n; pr.npad = (int)((n + 63) / 64 * 64); pr.c = c; pr.niter = pr.npad / 64;
+    pr.nu = (int)(n - c - 1); pr.grid = grid ? 1 : 0; pr.rowf = ((c + 2 + 3) / 4) * 4;
+    for (int k = -5; k <= 5; k++) pr.lam11[k + 5] = (float)pow(10.0, (double)(float)k);  // pyx:122,157-158
+    {
+        const int ctot = c + 1;
+        float r = (float)((0.5 * (double)(n - ctot)) * std::log(0.5 * (double)(n - ctot) / M_PI));  // pyx:1821
+        r = (float)((double)r - (0.5 * (double)(n - ctot)));                                          // pyx:1822
+        pr.logl_c = r;
+    }
+    pr.nhalf = (int)(n / 2);                                                                          // (n/2): C integer division
+    {
+        float r = (float)((double)(n / 2) * std::log((double)n / (2.0 * M_PI)));                      // pyx:1552
+        pr.ml_c = r - (float)(n / 2);                                                                 // pyx:1554
+    }
+    pr.leaf = ctx->plan.d_leaf; pr.node = ctx->plan.d_node; pr.level = ctx->plan.d_level; pr.chunk = ctx->plan.d_chunk;
+    pr.n_leaf = ctx->plan.n_leaf; pr.n_level = ctx->plan.n_level; pr.n_chunk = ctx->plan.n_chunk;
+    pr.n_vals = ctx->plan.n_leaf + ctx->plan.n_node;
+}
+
 // fixed rows + tables + the kernel for one (covariates, SNP block); Wr is n x c with row stride ldw >= c (the LRT's null model
 // passes the first c columns of a wider matrix)
 static int assoc_run(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, const float *Wr, int64_t ldw, const float *yr,
@@ -1325,8 +1524,7 @@ static int assoc_run(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, c
     if (rc) return rc;
 
     AssocParams pr{};
-    pr.n = (int)n; pr.npad = (int)((n + 63) / 64 * 64); pr.c = c; pr.niter = pr.npad / 64;
-    pr.nu = (int)(n - c - 1); pr.grid = grid ? 1 : 0; pr.rowf = ((c + 2 + 3) / 4) * 4;
+    fill_params(ctx, n, c, grid, pr);
     pr.p = p; pr.ldx = ldx; pr.xr = Xr;
     const int M = c + 2, NP = M * (M + 1) / 2;
     rc = ensure(ctx, &ctx->fixed, &ctx->fixed_bytes, (size_t)pr.npad * pr.rowf * 4);
@@ -1342,23 +1540,8 @@ static int assoc_run(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, c
     pr.fixg = (double *)((char *)ctx->tabs + off_fixg);
     pr.t1tab = (double *)((char *)ctx->tabs + off_t1);
     pr.ldHtab = (float *)((char *)ctx->tabs + off_ldh);
-    for (int k = -5; k <= 5; k++) pr.lam11[k + 5] = (float)pow(10.0, (double)(float)k);  // pyx:122,157-158
-    {
-        const int ctot = c + 1;
-        float r = (float)((0.5 * (double)(n - ctot)) * std::log(0.5 * (double)(n - ctot) / M_PI));  // pyx:1821
-        r = (float)((double)r - (0.5 * (double)(n - ctot)));                                          // pyx:1822
-        pr.logl_c = r;
-    }
     pr.lrt = lrt ? 1 : 0;
-    pr.nhalf = (int)(n / 2);                                                                          // (n/2): C integer division
-    {
-        float r = (float)((double)(n / 2) * std::log((double)n / (2.0 * M_PI)));                      // pyx:1552
-        pr.ml_c = r - (float)(n / 2);                                                                 // pyx:1554
-    }
     pr.lalt = lalt; pr.lamalt = lamalt;
-    pr.leaf = ctx->plan.d_leaf; pr.node = ctx->plan.d_node; pr.level = ctx->plan.d_level; pr.chunk = ctx->plan.d_chunk;
-    pr.n_leaf = ctx->plan.n_leaf; pr.n_level = ctx->plan.n_level; pr.n_chunk = ctx->plan.n_chunk;
-    pr.n_vals = ctx->plan.n_leaf + ctx->plan.n_node;
     pr.beta = beta; pr.se = se; pr.tau = tau; pr.lam = lambda; pr.F = F;
     pr.stats = stats_dev;
     pr.trace = lrt ? nullptr : ctx->eval_trace;
@@ -1417,6 +1600,116 @@ extern "C" int pg_assoc_set_eval_trace(pg_ctx *ctx, unsigned *trace_dev)
     PG_REQUIRE(ctx, "pg_assoc_set_eval_trace: NULL ctx");
     ctx->eval_trace = trace_dev;
     return PG_OK;
+}
+
+// ---- several phenotypes over one SNP block: pg_assoc_dev's results for each, with the decade scan's y-free entries shared ----------
+// Scratch of one call, in ctx->pheno: the fixed rows and fixg tables of a chunk of PHENO_CHUNK phenotypes, the phenotype-free tables
+// (h at the decade lambdas, t1, log|H|), and the scan buffer of a tile of SNPs (bounded: at most 256 MiB unless one SNP is more).
+struct PhenoLayout {
+    int npad, rowf, NP, tpad_max;
+    long long ptile;
+    size_t off_htab, off_fixg, off_t1, off_ldh, off_xbuf, bytes;
+};
+static PhenoLayout pheno_layout(int64_t n, int c, int t, int64_t p)
+{
+    PhenoLayout L{};
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    L.npad = (int)((n + 63) / 64 * 64); L.rowf = ((c + 2 + 3) / 4) * 4; L.NP = (c + 2) * (c + 3) / 2;
+    const int tc = t < PHENO_CHUNK ? t : PHENO_CHUNK;
+    L.tpad_max = 1;
+    while (L.tpad_max < tc) L.tpad_max <<= 1;
+    const size_t per_snp = (size_t)NLAM * 2 * (c + 1 + L.tpad_max) * 8;
+    const long long cap = (long long)((256u << 20) / per_snp);
+    L.ptile = p < cap ? p : (cap < 1024 ? 1024 : cap);
+    if (L.ptile > p) L.ptile = p;
+    L.off_htab = up((size_t)PHENO_CHUNK * L.npad * L.rowf * 4);
+    L.off_fixg = L.off_htab + up((size_t)NLAM * L.npad * 4);
+    L.off_t1 = L.off_fixg + up((size_t)PHENO_CHUNK * NLAM * 2 * L.NP * 8);
+    L.off_ldh = L.off_t1 + up(NLAM * 8);
+    L.off_xbuf = L.off_ldh + up(NLAM * 4);
+    L.bytes = L.off_xbuf + up((size_t)L.ptile * per_snp);
+    return L;
+}
+
+extern "C" int pg_assoc_pheno_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, int t, const float *d, const float *Wr,
+                                  const float *Yr, int64_t ldy, const float *Xr, int64_t ldx, int grid,
+                                  float *beta, float *se, float *tau, float *lambda, double *F, double *pval,
+                                  unsigned long long *stats_dev)
+{
+    PG_REQUIRE(ctx && d && Wr && Yr && Xr && beta && se && tau && lambda && F, "pg_assoc_pheno_dev: NULL argument");
+    PG_REQUIRE(n >= 2 && n < (1LL << 30) && p >= 0 && ldx >= n, "pg_assoc_pheno_dev: bad shape n=%lld p=%lld ldx=%lld",
+               (long long)n, (long long)p, (long long)ldx);
+    if (c < 1 || c > PG_MAX_COVARIATES) {
+        set_error("pg_assoc_pheno_dev: c=%d covariates not supported by this build (1..%d)", c, PG_MAX_COVARIATES);
+        return PG_ENOTSUP;
+    }
+    PG_REQUIRE(n - c - 1 > 0, "pg_assoc_pheno_dev: n - c - 1 must be positive");
+    PG_REQUIRE(t >= 1 && ldy >= n, "pg_assoc_pheno_dev: bad phenotypes t=%d ldy=%lld (n=%lld)", t, (long long)ldy, (long long)n);
+    if (p == 0) return PG_OK;
+    PG_HIP(hipSetDevice(ctx->device));
+    int rc = build_npsum_plan(ctx, n);
+    if (rc) return rc;
+    const PhenoLayout L = pheno_layout(n, c, t, p);
+    rc = ensure(ctx, &ctx->pheno, &ctx->pheno_bytes, L.bytes);
+    if (rc) return rc;
+    char *base = (char *)ctx->pheno;
+    float *fixed = (float *)base;
+    double *fixg = (double *)(base + L.off_fixg), *xbuf = (double *)(base + L.off_xbuf);
+
+    AssocParams pr{};
+    fill_params(ctx, n, c, grid, pr);
+    pr.ldx = ldx;
+    pr.htab = (float *)(base + L.off_htab);
+    pr.t1tab = (double *)(base + L.off_t1);
+    pr.ldHtab = (float *)(base + L.off_ldh);
+    pr.stats = stats_dev;
+    const size_t fixed_stride = (size_t)L.npad * L.rowf, fixg_stride = (size_t)NLAM * 2 * L.NP;
+    for (int k0 = 0; k0 < t; k0 += PHENO_CHUNK) {
+        const int tcn = (t - k0) < PHENO_CHUNK ? (t - k0) : PHENO_CHUNK;
+        int tpad = 1;
+        while (tpad < tcn) tpad <<= 1;
+        // per phenotype: its fixed rows [d, W, y_k] and its W,y Gram entries at the decade lambdas (the h, t1 and log|H| tables the
+        // setups write are the same for every phenotype)
+        for (int j = 0; j < tcn; j++) {
+            pr.fixed = fixed + j * fixed_stride;
+            pr.fixg = fixg + j * fixg_stride;
+            build_fixed_kernel<<<(L.npad + 255) / 256, 256, 0, ctx->stream>>>(pr.n, L.npad, c, c, L.rowf, d, Wr, Yr + (size_t)(k0 + j) * ldy,
+                                                                             (float *)pr.fixed);
+            PG_HIP(hipGetLastError());
+            rc = launch_assoc_pheno(ctx, pr, PhenoLaunch{PhenoLaunch::SETUP, nullptr, 0, 0, 0, nullptr});
+            if (rc) return rc;
+        }
+        pr.xe = c + 1 + tpad; pr.xbuf = xbuf;
+        for (int64_t s0 = 0; s0 < p; s0 += L.ptile) {
+            pr.p = (p - s0) < L.ptile ? (p - s0) : L.ptile;
+            pr.xr = Xr + (size_t)s0 * ldx;
+            rc = launch_assoc_pheno(ctx, pr, PhenoLaunch{PhenoLaunch::SCAN, Yr + (size_t)k0 * ldy, ldy, tcn, tpad, xbuf});
+            if (rc) return rc;
+            for (int j = 0; j < tcn; j++) {
+                const size_t o = (size_t)(k0 + j) * p + s0;
+                pr.fixed = fixed + j * fixed_stride; pr.fixg = fixg + j * fixg_stride; pr.xcol = c + 1 + j;
+                pr.beta = beta + o; pr.se = se + o; pr.tau = tau + o; pr.lam = lambda + o; pr.F = F + o;
+                rc = launch_assoc_pheno(ctx, pr, PhenoLaunch{PhenoLaunch::SEARCH, nullptr, 0, tcn, tpad, xbuf});
+                if (rc) return rc;
+            }
+        }
+    }
+    if (pval) return pg_fdist_sf_dev(ctx, (int64_t)t * p, F, (double)(n - c - 1), pval);
+    return PG_OK;
+}
+
+// pg_assoc_warm for pg_assoc_pheno_dev: the float32-sum plan and the scratch of a call with t phenotypes over up to p SNPs
+extern "C" int pg_assoc_pheno_warm(pg_ctx *ctx, int64_t n, int c, int t, int64_t p)
+{
+    PG_REQUIRE(ctx && n >= 2 && n < (1LL << 30) && t >= 1 && p >= 1, "pg_assoc_pheno_warm: bad arguments");
+    if (c < 1 || c > PG_MAX_COVARIATES) {
+        set_error("pg_assoc_pheno_warm: c=%d covariates not supported by this build (1..%d)", c, PG_MAX_COVARIATES);
+        return PG_ENOTSUP;
+    }
+    PG_HIP(hipSetDevice(ctx->device));
+    int rc = build_npsum_plan(ctx, n);
+    if (rc) return rc;
+    return ensure(ctx, &ctx->pheno, &ctx->pheno_bytes, pheno_layout(n, c, t, p).bytes);
 }
 
 namespace pg {

@@ -37,7 +37,7 @@ from .bed import PackedBed
 from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_restricted, newton, the *_overload scalars)
 from . import model as _model
 
-__all__ = ["pygemma", "SampleIter", "pinned_empty", "pin", "kinship"] + _model.__all__
+__all__ = ["pygemma", "pygemma_multi", "SampleIter", "pinned_empty", "pin", "kinship"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -235,8 +235,10 @@ class _Prefetch:
         self.ctxs = []
 
 
-def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out, errs, verbose, ckpt=None, stats=None, pre=None):
-    """One GPU: SNP columns [a,b) of X through (rotate | transpose) -> assoc, in batches.  Two host threads per GPU, each with
+def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out, errs, verbose, ckpt=None, stats=None, pre=None,
+               npheno=0):
+    """One GPU: SNP columns [a,b) of X through (rotate | transpose) -> assoc, in batches.  With `npheno` > 0, yr holds that many
+    rotated phenotypes (npheno, n) and every batch, transported and rotated once, goes through pg_assoc_pheno_dev for all of them.  Two host threads per GPU, each with
     its own stream, device buffers and pinned staging, take batches from a shared list, so that the host->device DMA of one
     batch overlaps the kernels of the other.  `dU`: GPU 0's resident eigenvectors (device 0) or None; with a communicator the
     other GPUs receive them by RCCL broadcast.  With `ckpt` every finished batch is written to disk (and batches found there,
@@ -272,7 +274,7 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
             p = X.shape[1]
             direct = (not packed) and _lib.is_pinned(X)        # X itself is page-locked: DMA straight out of it
             snp_major = (not packed) and X.flags.f_contiguous and not X.flags.c_contiguous     # (float32 only: pygemma() sees to it)
-            nout = 32 + (32 if lrt else 0)                      # result bytes per SNP
+            nout = 32 * npheno if npheno else 32 + (32 if lrt else 0)   # result bytes per SNP
             todo = []
             for s in range(a, b, pb_max):
                 e = min(s + pb_max, b)
@@ -308,7 +310,10 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
                         dXf = None       # float32 image of an 8-bit block, only if one does not qualify for the genotype path
                         stg = _Staging(ctx, L, 0 if direct else raw_bytes, pb_max * nout)
                         hres = (C.c_char * (pb_max * nout)).from_address(stg.out)
-                        _lib.check(L.pg_assoc_warm(ctx.handle, n, c), "pg_assoc_warm")      # the first batch's kernels then queue without a host stall
+                        if npheno:
+                            _lib.check(L.pg_assoc_pheno_warm(ctx.handle, n, c, npheno, pb_max), "pg_assoc_pheno_warm")
+                        else:
+                            _lib.check(L.pg_assoc_warm(ctx.handle, n, c), "pg_assoc_warm")      # the first batch's kernels then queue without a host stall
                         if stats is not None:
                             with lock:
                                 stats["worker_alloc_s"] = max(stats.get("worker_alloc_s", 0.0), time.time() - t_w)
@@ -377,7 +382,12 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
                                     _lib.check(L.pg_transpose_dev(ctx.handle, n, pb, dXc.ptr, ldX, dXr.ptr, ldx), "pg_transpose_dev")
                                 # result block: [F | p | beta | se | tau | lambda] (+ [l_alt | l_null | D_lrt | p_lrt] f64 with lrt)
                                 r0 = dres.ptr
-                                if lrt:
+                                if npheno:       # the same block per phenotype-major row: [F | p | beta | se | tau | lambda], each npheno x pb
+                                    tp = npheno * pb
+                                    _lib.check(L.pg_assoc_pheno_dev(ctx.handle, n, c, pb, npheno, dd.ptr, dW.ptr, dy.ptr, n, dXr.ptr, ldx, int(grid),
+                                                                    r0 + 16 * tp, r0 + 20 * tp, r0 + 24 * tp, r0 + 28 * tp, r0, r0 + 8 * tp, None),
+                                               "pg_assoc_pheno_dev")
+                                elif lrt:
                                     _lib.check(L.pg_assoc_lrt_dev(ctx.handle, n, c, pb, dd.ptr, dW.ptr, dy.ptr, dXr.ptr, ldx, int(grid),
                                                                   r0 + 16 * pb, r0 + 20 * pb, r0 + 24 * pb, r0 + 28 * pb, r0, r0 + 8 * pb,
                                                                   r0 + 32 * pb, r0 + 40 * pb, r0 + 48 * pb, r0 + 56 * pb), "pg_assoc_lrt_dev")
@@ -392,11 +402,19 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
                                 with lock:
                                     stats["prefetched_batches"] = stats.get("prefetched_batches", 0) + 1
                             hb = np.frombuffer(hres, np.uint8, pb * nout)
-                            FP = hb[:16 * pb].view(np.float64).reshape(2, pb)
-                            res = hb[16 * pb:32 * pb].view(np.float32).reshape(4, pb)
-                            out["beta"][s:e], out["se_beta"][s:e], out["tau"][s:e] = res[0], res[1], res[2]
-                            out["lambda"][s:e] = res[3].astype(np.float64)
-                            out["F_wald"][s:e], out["p_wald"][s:e] = FP[0], FP[1]
+                            if npheno:
+                                tp = npheno * pb
+                                FP = hb[:16 * tp].view(np.float64).reshape(2, npheno, pb)
+                                res = hb[16 * tp:32 * tp].view(np.float32).reshape(4, npheno, pb)
+                                out["beta"][:, s:e], out["se_beta"][:, s:e], out["tau"][:, s:e] = res[0], res[1], res[2]
+                                out["lambda"][:, s:e] = res[3].astype(np.float64)
+                                out["F_wald"][:, s:e], out["p_wald"][:, s:e] = FP[0], FP[1]
+                            else:
+                                FP = hb[:16 * pb].view(np.float64).reshape(2, pb)
+                                res = hb[16 * pb:32 * pb].view(np.float32).reshape(4, pb)
+                                out["beta"][s:e], out["se_beta"][s:e], out["tau"][s:e] = res[0], res[1], res[2]
+                                out["lambda"][s:e] = res[3].astype(np.float64)
+                                out["F_wald"][s:e], out["p_wald"][s:e] = FP[0], FP[1]
                             if lrt:
                                 LR = hb[32 * pb:64 * pb].view(np.float64).reshape(4, pb)
                                 for k, col in enumerate(_LRT_COLS):
@@ -524,6 +542,58 @@ def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=Fa
     if de:
         # calculate_de is broken upstream (unpacks 4 of SampleIter's 5-tuple, lmm/lmm.py:499 vs :434)
         raise NotImplementedError("de=True is broken in the reference (lmm/lmm.py:499) and is not provided")
+    out = _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint, lrt, eigenpairs, stats, 0)
+    cols = list(_COLS) + (list(_LRT_COLS) if lrt else [])
+    results_df = pd.DataFrame(out, columns=cols)                                                     # lmm.py:403
+    if snps is not None:
+        results_df["SNPs"] = snps                                                                    # lmm.py:408-409
+    return results_df
+
+
+def pygemma_multi(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, grid=False, eigen=True, nproc=1,
+                  eigenpairs=None, stats=None):
+    """lmm.pygemma for several phenotypes over the same X, W and K (the loop the reference's callers write by hand:
+    experiments/wtccc/run_pygemma_imputed.py:516-532, experiments/animal_gwas/run_gwas.py:167-175).
+
+    Y: (n, t) array or DataFrame, or (n,); every column is cast to float32 as lmm.pygemma casts its Y (lmm.py:115-116).
+    Returns a dict in column order — keys: Y's column labels for a DataFrame, else 0..t-1 — of DataFrames that are
+    bit-identical to lmm.pygemma(Y[:, k], X, W, K, ...) with the same arguments.  The eigendecomposition, the transport and
+    rotation of every SNP batch and the phenotype-free part of the decade scan are done once for all phenotypes.  Samples are
+    never dropped per phenotype: a NaN phenotype yields the rows a single run would give (disable_checks=False raises instead),
+    the other phenotypes are unaffected — mean-impute missing values beforehand as the reference's callers do.  No lrt,
+    checkpoint or de.  `stats` receives lmm.pygemma's counters plus `phenotypes`."""
+    if isinstance(Y, pd.DataFrame):
+        labels = list(Y.columns)
+        cols = [np.asarray(Y.iloc[:, k]) for k in range(Y.shape[1])]
+    else:
+        Ya = np.asarray(Y)
+        if Ya.ndim == 1:
+            Ya = Ya.reshape(-1, 1)
+        if Ya.ndim != 2:
+            raise ValueError(f"Y must be (n,) or (n, t), got shape {Ya.shape}")
+        labels = list(range(Ya.shape[1]))
+        cols = [Ya[:, k] for k in range(Ya.shape[1])]
+    if not cols:
+        raise ValueError("Y has no phenotype columns")
+    n = X.shape[0]
+    if cols[0].shape[0] != n:
+        raise ValueError(f"shape mismatch: Y has {cols[0].shape[0]} rows, X {n}")
+    Y32 = np.empty((n, len(cols)), np.float32)
+    for k, col in enumerate(cols):
+        Y32[:, k] = col.astype(np.float32)                   # lmm.py:115-116, per column
+    out = _scan(Y32, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, None, False, eigenpairs, stats, len(cols))
+    res = {}
+    for k, lab in enumerate(labels):
+        df = pd.DataFrame({col: out[col][k] for col in _COLS}, columns=list(_COLS))
+        if snps is not None:
+            df["SNPs"] = snps
+        res[lab] = df
+    return res
+
+
+def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint, lrt, eigenpairs, stats, npheno):
+    """The pipeline under pygemma (npheno = 0: Y is one phenotype) and pygemma_multi (Y: float32 (n, npheno)).  Returns the
+    result columns: arrays of p values, or npheno x p with npheno > 0."""
     L = _lib.load()
     packed = isinstance(X, PackedBed)                         # extension (SURVEY 8f N4): a PLINK .bed image instead of the float matrix
     if packed and not eigen:
@@ -557,6 +627,7 @@ def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=Fa
         X = np.ascontiguousarray(X)
     n, p = X.shape
     c = W.shape[1]
+    ty = npheno or 1                                         # phenotype columns of Y that are used
     if Y.shape[0] != n or W.shape[0] != n:
         raise ValueError(f"shape mismatch: Y {Y.shape}, X {X.shape}, W {W.shape}")
     ngpu = _lib.device_count()
@@ -652,8 +723,9 @@ def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=Fa
                     _log(verbose, f"Eigendecomposition computed - {time.time() - t0:.3f} s")
                 assert (eigenVals >= 0).all()                    # lmm.py:162
                 t1 = time.time()
-                YW = _rotate_small(ectx, L, n, dU0, np.concatenate([Y.reshape(n, -1)[:, :1], W], axis=1))
-                Yr, Wr = YW[:, :1], np.ascontiguousarray(YW[:, 1:])
+                # [Y | W] in one rotation: an output column's bits do not depend on the columns beside it (rotate.hip)
+                YW = _rotate_small(ectx, L, n, dU0, np.concatenate([Y.reshape(n, -1)[:, :ty], W], axis=1))
+                Yr, Wr = YW[:, :ty], np.ascontiguousarray(YW[:, ty:])
                 _log(verbose, f"Left multiplied Y, W by U.T - {time.time() - t1:.3f} s")
             except BaseException:
                 if pre is not None:
@@ -666,7 +738,7 @@ def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=Fa
             eigenVals = np.maximum(0.0, K).astype(np.float32).reshape(-1)   # lmm.py:166-167
             if eigenVals.shape[0] != n:
                 raise ValueError(f"with eigen=False K must hold the {n} eigenvalues, got {K.shape}")
-            Yr, Wr = Y.reshape(n, -1)[:, :1], np.ascontiguousarray(W)
+            Yr, Wr = Y.reshape(n, -1)[:, :ty], np.ascontiguousarray(W)
 
         if not disable_checks:
             # lmm.py:253-256 (the reference tests the rotated arrays; a NaN anywhere in a raw column makes that
@@ -681,15 +753,18 @@ def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=Fa
                 raise ValueError("NaNs present in data")
 
         _log(verbose, f"Running {p} SNPs with {n} individuals on {ndev} GPU(s)...")
-        out = {"beta": np.empty(p, np.float32), "se_beta": np.empty(p, np.float32), "tau": np.empty(p, np.float32),
-               "lambda": np.empty(p, np.float64), "F_wald": np.empty(p, np.float64), "p_wald": np.empty(p, np.float64)}
+        shp = (npheno, p) if npheno else p
+        out = {"beta": np.empty(shp, np.float32), "se_beta": np.empty(shp, np.float32), "tau": np.empty(shp, np.float32),
+               "lambda": np.empty(shp, np.float64), "F_wald": np.empty(shp, np.float64), "p_wald": np.empty(shp, np.float64)}
         if lrt:
             for col in _LRT_COLS:
                 out[col] = np.empty(p, np.float64)
         errs, threads = [], []
         if stats is not None:
             stats.update({"batches": 0, "bytes_in": 0, "batch_s": 0.0, "gpus": ndev})
-        yr1 = np.ascontiguousarray(Yr.reshape(-1), np.float32)
+            if npheno:
+                stats["phenotypes"] = npheno
+        yr1 = np.ascontiguousarray(Yr.T if npheno else Yr.reshape(-1), np.float32)    # (npheno, n): phenotype-major rows
         if checkpoint:
             os.makedirs(checkpoint, exist_ok=True)
             # identity of the run: shapes, options, batch geometry and the SNP-independent inputs themselves (rotated y, W and the
@@ -739,7 +814,7 @@ def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=Fa
             for dev_id, (a, b) in enumerate(blocks):
                 th = threading.Thread(target=_run_block, args=(dev_id, a, b, n, c, eigenVals, Wr, yr1, X,
                                                                dUs[dev_id], comms[dev_id] if comms else None,
-                                                               grid, eigen, lrt, out, errs, verbose, checkpoint, stats, pre))
+                                                               grid, eigen, lrt, out, errs, verbose, checkpoint, stats, pre, npheno))
                 th.start()
                 threads.append(th)
             for th in threads:
@@ -781,8 +856,4 @@ def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=Fa
     if stats is not None:
         stats["seconds"] = time.time() - t2
     _log(verbose, f"Finished testing {p} SNPs in {time.time() - t2:.3f} s")
-    cols = list(_COLS) + (list(_LRT_COLS) if lrt else [])
-    results_df = pd.DataFrame(out, columns=cols)                                                     # lmm.py:403
-    if snps is not None:
-        results_df["SNPs"] = snps                                                                    # lmm.py:408-409
-    return results_df
+    return out
