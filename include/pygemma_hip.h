@@ -164,6 +164,21 @@ int pg_assoc_lrt_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, c
                      const float *Xr, int64_t ldx, int grid, float *beta, float *se, float *tau, float *lambda,
                      double *F, double *pval, double *l_alt, double *l_null, double *D_lrt, double *p_lrt);
 
+/* ---- The score test (GEMMA's -lmm 3: the score statistic at the null model's ML lambda), a first screen over a whole genome:
+ * lambda is fitted once, on y ~ W, and every SNP is evaluated at it — no per-SNP search, one pass over the rotated X.
+ *   pg_score_null_dev : lambda0 = the ML lambda of y ~ W, calc_lambda(eigenVals, Y, W) (lmm/lmm.py:22-84); the null search of
+ *                       pg_assoc_lrt_dev (Brent); one float32 into lambda0_dev (device)
+ *   pg_score_dev      : with h = 1/(lambda0 d + 1), G = W'HW, P0 = H - HW G^-1 W'H (all fp64; Cholesky of G):
+ *                       P_xx = x'P0x, P_xy = x'P0y, P_yy = y'P0y, Px_yy = P_yy - P_xy^2 / P_xx, df = n - c - 1;
+ *                       beta = P_xy / P_xx, se = sqrt(Px_yy / (df P_xx)), tau = df / Px_yy, lambda = lambda0 (float32 each),
+ *                       F = n P_xy^2 / (P_yy P_xx), pval = F(1, df).sf(F) (float64; pval may be NULL).
+ *                       A SNP with P_xx <= 1e-10 x'Hx (constant, in span(W)) or a non-finite x gets NaN in every column but lambda;
+ *                       so does every SNP when the Cholesky of G fails (W rank-deficient).  A row depends only on its SNP.
+ * Same argument checks as pg_assoc_dev. */
+int pg_score_null_dev(pg_ctx *ctx, int64_t n, int c, const float *d, const float *Wr, const float *yr, float *lambda0_dev);
+int pg_score_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, const float *Wr, const float *yr, float lambda0,
+                 const float *Xr, int64_t ldx, float *beta, float *se, float *tau, float *lambda, double *F, double *pval);
+
 /* host-pointer convenience: X in the REFERENCE layout (n x p row-major, already rotated), as
  * calculate() receives it; transposed to SNP-major on the device. */
 int pg_assoc(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, const float *Wr, const float *yr,

@@ -23,7 +23,7 @@ SYMBOLS = [
     "pg_comm_unique_id", "pg_comm_init_rank", "pg_comm_init_all", "pg_comm_destroy", "pg_comm_size", "pg_comm_rank",
     "pg_comm_broadcast_dev", "pg_comm_allgather_dev", "pg_comm_allreduce_f64_dev", "pg_comm_barrier", "pg_comm_group_start",
     "pg_comm_group_end", "pgx_dgemm_dev", "pgx_sytrd_dev", "pgx_stedc_dev", "pgx_sb2_stage1_dev", "pgx_sb2_stage2_dev", "pgx_sb2_set_debug", "pg_kinship_geno_dev", "pg_assoc_lrt_dev", "pg_rotate_auto_dev", "pg_assoc_set_eval_trace", "pg_assoc_warm", "pg_rotate_auto_i8_dev",
-    "pg_zkzt_dev", "pgx_dgemm_ex_dev", "pgx_ring_stamps", "pg_assoc_pheno_dev", "pg_assoc_pheno_warm",
+    "pg_zkzt_dev", "pgx_dgemm_ex_dev", "pgx_ring_stamps", "pg_assoc_pheno_dev", "pg_assoc_pheno_warm", "pg_score_null_dev", "pg_score_dev",
 ]
 
 
@@ -84,6 +84,10 @@ def load():
     L.pg_assoc_pheno_dev.restype = i32
     L.pg_assoc_pheno_warm.argtypes = [vp, i64, i32, i32, i64]
     L.pg_assoc_pheno_warm.restype = i32
+    L.pg_score_null_dev.argtypes = [vp, i64, i32, vp, vp, vp, vp]
+    L.pg_score_null_dev.restype = i32
+    L.pg_score_dev.argtypes = [vp, i64, i32, i64, vp, vp, vp, C.c_float, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.pg_score_dev.restype = i32
     L.pg_rotate_auto_i8_dev.argtypes = [vp, i64, i64, vp, vp, i32, i64, vp, i64, vp, vp]
     L.pg_rotate_auto_i8_dev.restype = i32
     L.pg_rotate_auto_dev.argtypes = [vp, i64, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp]

@@ -1771,6 +1771,32 @@ extern "C" int pg_assoc_lrt_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, const 
     return PG_OK;
 }
 
+// ---- the score test's null model (score.hip): lambda0 = the ML lambda of y ~ W, calc_lambda(eigenVals, Y, W) (lmm/lmm.py:22-84).
+// It is pg_assoc_lrt_dev's null search: c - 1 covariates with the last one in the SNP's place, the ML search appended; its
+// lambda lands in lambda0_dev (one float32, device).
+extern "C" int pg_score_null_dev(pg_ctx *ctx, int64_t n, int c, const float *d, const float *Wr, const float *yr, float *lambda0_dev)
+{
+    PG_REQUIRE(ctx && d && Wr && yr && lambda0_dev, "pg_score_null_dev: NULL argument");
+    PG_REQUIRE(n >= 2 && n < (1LL << 30), "pg_score_null_dev: bad shape n=%lld", (long long)n);
+    if (c < 1 || c > PG_MAX_COVARIATES) {
+        set_error("pg_score_null_dev: c=%d covariates not supported by this build (1..%d)", c, PG_MAX_COVARIATES);
+        return PG_ENOTSUP;
+    }
+    PG_REQUIRE(n - c - 1 > 0, "pg_score_null_dev: n - c - 1 must be positive");
+    PG_HIP(hipSetDevice(ctx->device));
+    const int64_t npad = (n + 63) / 64 * 64;
+    // scratch: [x_null (npad f32) | outputs of the one-SNP run: 4 f32 + 1 f64 | its log-likelihood f32]
+    const size_t off_out = (size_t)npad * 4;
+    int rc = ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, off_out + 64);
+    if (rc) return rc;
+    char *sc = (char *)ctx->scratch;
+    float *xnull = (float *)sc, *nb = (float *)(sc + off_out), *lnull = nb + 8;
+    double *nF = (double *)(sc + off_out + 16);
+    gather_col_kernel<<<(unsigned)((npad + 255) / 256), 256, 0, ctx->stream>>>((int)n, (int)npad, Wr, c, c - 1, xnull);
+    PG_HIP(hipGetLastError());
+    return assoc_run(ctx, n, c - 1, 1, d, Wr, c, yr, xnull, npad, 0, nb, nb + 1, nb + 2, nb + 3, nF, nullptr, true, lnull, lambda0_dev);
+}
+
 // ---- inspection surface ----------------------------------------------------------------------------------------------
 static int inspect_params(pg_ctx *ctx, int64_t n, int ctot, InspectParams &ip, const float *d)
 {

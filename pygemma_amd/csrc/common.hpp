@@ -54,6 +54,7 @@ struct pg_ctx {
     unsigned *eval_trace = nullptr;                  // caller-owned (pg_assoc_set_eval_trace)
     pg::NpSumPlan plan;
     void *pheno = nullptr; size_t pheno_bytes = 0;   // pg_assoc_pheno_dev: per-phenotype tables + the shared scan buffer
+    void *score = nullptr; size_t score_bytes = 0;   // pg_score_dev: the fixed vectors h, B, P0 y and P_yy
     // generic scratch
     void *scratch = nullptr; size_t scratch_bytes = 0;
     // the eigensolver's work arena, kept between solves up to 16 GiB (n <= ~14 000): a hipMalloc / hipFree pair

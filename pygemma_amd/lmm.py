@@ -37,7 +37,7 @@ from .bed import PackedBed
 from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_restricted, newton, the *_overload scalars)
 from . import model as _model
 
-__all__ = ["pygemma", "pygemma_multi", "SampleIter", "pinned_empty", "pin", "kinship"] + _model.__all__
+__all__ = ["pygemma", "pygemma_multi", "pygemma_score", "SampleIter", "pinned_empty", "pin", "kinship"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -236,9 +236,11 @@ class _Prefetch:
 
 
 def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out, errs, verbose, ckpt=None, stats=None, pre=None,
-               npheno=0):
+               npheno=0, lam0=None):
     """One GPU: SNP columns [a,b) of X through (rotate | transpose) -> assoc, in batches.  With `npheno` > 0, yr holds that many
-    rotated phenotypes (npheno, n) and every batch, transported and rotated once, goes through pg_assoc_pheno_dev for all of them.  Two host threads per GPU, each with
+    rotated phenotypes (npheno, n) and every batch, transported and rotated once, goes through pg_assoc_pheno_dev for all of them.
+    With `lam0` (the null model's float32 ML lambda, the same for every GPU) every batch goes through pg_score_dev instead, into the
+    same result rows [F | p | beta | se | tau | lambda].  Two host threads per GPU, each with
     its own stream, device buffers and pinned staging, take batches from a shared list, so that the host->device DMA of one
     batch overlaps the kernels of the other.  `dU`: GPU 0's resident eigenvectors (device 0) or None; with a communicator the
     other GPUs receive them by RCCL broadcast.  With `ckpt` every finished batch is written to disk (and batches found there,
@@ -312,7 +314,7 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
                         hres = (C.c_char * (pb_max * nout)).from_address(stg.out)
                         if npheno:
                             _lib.check(L.pg_assoc_pheno_warm(ctx.handle, n, c, npheno, pb_max), "pg_assoc_pheno_warm")
-                        else:
+                        elif lam0 is None:
                             _lib.check(L.pg_assoc_warm(ctx.handle, n, c), "pg_assoc_warm")      # the first batch's kernels then queue without a host stall
                         if stats is not None:
                             with lock:
@@ -387,6 +389,9 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
                                     _lib.check(L.pg_assoc_pheno_dev(ctx.handle, n, c, pb, npheno, dd.ptr, dW.ptr, dy.ptr, n, dXr.ptr, ldx, int(grid),
                                                                     r0 + 16 * tp, r0 + 20 * tp, r0 + 24 * tp, r0 + 28 * tp, r0, r0 + 8 * tp, None),
                                                "pg_assoc_pheno_dev")
+                                elif lam0 is not None:
+                                    _lib.check(L.pg_score_dev(ctx.handle, n, c, pb, dd.ptr, dW.ptr, dy.ptr, float(lam0), dXr.ptr, ldx,
+                                                              r0 + 16 * pb, r0 + 20 * pb, r0 + 24 * pb, r0 + 28 * pb, r0, r0 + 8 * pb), "pg_score_dev")
                                 elif lrt:
                                     _lib.check(L.pg_assoc_lrt_dev(ctx.handle, n, c, pb, dd.ptr, dW.ptr, dy.ptr, dXr.ptr, ldx, int(grid),
                                                                   r0 + 16 * pb, r0 + 20 * pb, r0 + 24 * pb, r0 + 28 * pb, r0, r0 + 8 * pb,
@@ -591,9 +596,40 @@ def pygemma_multi(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True,
     return res
 
 
-def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint, lrt, eigenpairs, stats, npheno):
-    """The pipeline under pygemma (npheno = 0: Y is one phenotype) and pygemma_multi (Y: float32 (n, npheno)).  Returns the
-    result columns: arrays of p values, or npheno x p with npheno > 0."""
+def pygemma_score(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, eigen=True, nproc=1, eigenpairs=None, stats=None):
+    """Score test over every SNP at the null model's ML lambda (GEMMA's -lmm 3) — the usual first screen of a whole genome: score
+    everything, then run lmm.pygemma (Wald, or lrt=True) on the hits.  Same inputs as lmm.pygemma (Y, X, W, K, Z, snps, eigen,
+    nproc, eigenpairs; every X kind it takes).
+
+    lambda0 = the ML lambda of y ~ W (calc_lambda, lmm/lmm.py:22-84) is fitted once, on GPU 0, and every SNP is evaluated at it:
+    with h = 1/(lambda0 d + 1) and P0 = H - HW (W'HW)^-1 W'H in the eigenbasis (fp64), P_xx = x'P0x, P_xy = x'P0y, P_yy = y'P0y,
+    Px_yy = P_yy - P_xy^2/P_xx, df = n - c - 1:
+      beta = P_xy/P_xx, se_beta = sqrt(Px_yy/(df P_xx)), tau = df/Px_yy, lambda = lambda0   (float32; float64 for lambda)
+      F_score = n P_xy^2/(P_yy P_xx), p_score = F(1, df).sf(F_score)                        (float64)
+    A SNP that is constant or lies in span(W) (P_xx <= 1e-10 x'Hx), or holds a NaN/inf, gets NaN in every column but lambda; a
+    rank-deficient W gives NaN rows throughout.  No grid (the null search is Brent's), lrt or checkpoint.  `stats` receives
+    lmm.pygemma's counters plus `lambda_null`."""
+    out = _scan(Y, X, W, K, Z, verbose, disable_checks, False, eigen, nproc, None, False, eigenpairs, stats, 0, score=True)
+    results_df = pd.DataFrame({"beta": out["beta"], "se_beta": out["se_beta"], "tau": out["tau"], "lambda": out["lambda"],
+                               "F_score": out["F_wald"], "p_score": out["p_wald"]})
+    if snps is not None:
+        results_df["SNPs"] = snps
+    return results_df
+
+
+def _null_lambda(L, n, c, d, Wr, yr):
+    """lambda0 of the score test: the ML lambda of y ~ W on GPU 0 (pg_score_null_dev), read back as one float32."""
+    with _lib.Context(0) as ctx:
+        dd, dW, dy, dl = ctx.to_device(d), ctx.to_device(Wr), ctx.to_device(yr), ctx.alloc(4)
+        _lib.check(L.pg_score_null_dev(ctx.handle, n, c, dd.ptr, dW.ptr, dy.ptr, dl.ptr), "pg_score_null_dev")
+        ctx.sync()
+        return np.float32(dl.download((1,), np.float32)[0])
+
+
+def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint, lrt, eigenpairs, stats, npheno, score=False):
+    """The pipeline under pygemma (npheno = 0: Y is one phenotype), pygemma_multi (Y: float32 (n, npheno)) and pygemma_score
+    (score = True: F_wald / p_wald hold F_score / p_score).  Returns the result columns: arrays of p values, or npheno x p with
+    npheno > 0."""
     L = _lib.load()
     packed = isinstance(X, PackedBed)                         # extension (SURVEY 8f N4): a PLINK .bed image instead of the float matrix
     if packed and not eigen:
@@ -630,6 +666,11 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
     ty = npheno or 1                                         # phenotype columns of Y that are used
     if Y.shape[0] != n or W.shape[0] != n:
         raise ValueError(f"shape mismatch: Y {Y.shape}, X {X.shape}, W {W.shape}")
+    if score:
+        if W.ndim != 2 or not 1 <= c <= 30:
+            raise ValueError(f"the score test takes 1 to 30 covariates, got W {W.shape}")
+        if n - c - 1 <= 0:
+            raise ValueError(f"the score test needs n - c - 1 > 0 (n = {n}, c = {c})")
     ngpu = _lib.device_count()
     if ngpu < 1:
         raise _lib.PgError("no MI355X visible: pygemma_amd has no CPU path")
@@ -765,6 +806,12 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
             if npheno:
                 stats["phenotypes"] = npheno
         yr1 = np.ascontiguousarray(Yr.T if npheno else Yr.reshape(-1), np.float32)    # (npheno, n): phenotype-major rows
+        lam0 = None
+        if score:      # once per call, on GPU 0; every GPU's shard gets the same float
+            lam0 = _null_lambda(L, n, c, eigenVals, np.ascontiguousarray(Wr, np.float32), yr1)
+            _log(verbose, f"Null model: lambda0 = {float(lam0):.6g}")
+            if stats is not None:
+                stats["lambda_null"] = float(lam0)
         if checkpoint:
             os.makedirs(checkpoint, exist_ok=True)
             # identity of the run: shapes, options, batch geometry and the SNP-independent inputs themselves (rotated y, W and the
@@ -814,7 +861,7 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
             for dev_id, (a, b) in enumerate(blocks):
                 th = threading.Thread(target=_run_block, args=(dev_id, a, b, n, c, eigenVals, Wr, yr1, X,
                                                                dUs[dev_id], comms[dev_id] if comms else None,
-                                                               grid, eigen, lrt, out, errs, verbose, checkpoint, stats, pre, npheno))
+                                                               grid, eigen, lrt, out, errs, verbose, checkpoint, stats, pre, npheno, lam0))
                 th.start()
                 threads.append(th)
             for th in threads:

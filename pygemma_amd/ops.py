@@ -37,6 +37,47 @@ def assoc(d, Wr, yr, Xr, grid=False, ctx=None, want_p=True, return_stats=False):
             ctx.close()
 
 
+def score(d, Wr, yr, Xr, lam0=None, ctx=None):
+    """The score test at the null model's ML lambda (pg_score_null_dev + pg_score_dev) on the GPU.
+    d (n,), Wr (n,c), yr (n,) or (n,1), Xr (n,p) in the REFERENCE layout, all in the eigenbasis.  lam0: the float32 lambda to
+    evaluate at (None: the ML lambda of y ~ W, computed on the device).  Returns dict(beta, se_beta, tau, lambda, F_score,
+    p_score, lambda_null)."""
+    L = _lib.load()
+    own = ctx is None
+    ctx = ctx or _lib.Context(0)
+    try:
+        d, Wr, yr, Xr = _f32(d), _f32(Wr), _f32(np.asarray(yr).reshape(-1)), _f32(Xr)
+        n, c = Wr.shape
+        p = Xr.shape[1]
+        assert d.shape == (n,) and yr.shape == (n,) and Xr.shape[0] == n
+        dd, dW, dy = ctx.to_device(d), ctx.to_device(Wr), ctx.to_device(yr)
+        if lam0 is None:
+            dl = ctx.alloc(4)
+            _lib.check(L.pg_score_null_dev(ctx.handle, n, c, dd.ptr, dW.ptr, dy.ptr, dl.ptr), "pg_score_null_dev")
+            ctx.sync()
+            lam0 = dl.download((1,), np.float32)[0]
+            dl.free()
+        lam0 = np.float32(lam0)
+        dX = ctx.to_device(Xr)
+        dXr = ctx.alloc(max(p, 1) * n * 4)
+        out = [ctx.alloc(max(p, 1) * 4) for _ in range(4)] + [ctx.alloc(max(p, 1) * 8) for _ in range(2)]
+        if p:
+            _lib.check(L.pg_transpose_dev(ctx.handle, n, p, dX.ptr, p, dXr.ptr, n), "pg_transpose_dev")
+        _lib.check(L.pg_score_dev(ctx.handle, n, c, p, dd.ptr, dW.ptr, dy.ptr, float(lam0), dXr.ptr, n, *[b.ptr for b in out]),
+                   "pg_score_dev")
+        ctx.sync()
+        res = {col: b.download((p,), np.float32 if k < 4 else np.float64)
+               for k, (col, b) in enumerate(zip(("beta", "se_beta", "tau", "lambda", "F_score", "p_score"), out))}
+        res["lambda"] = res["lambda"].astype(np.float64)
+        res["lambda_null"] = float(lam0)
+        for b in (dd, dW, dy, dX, dXr, *out):
+            b.free()
+        return res
+    finally:
+        if own:
+            ctx.close()
+
+
 def fdist_sf(F, dfd, ctx=None):
     L = _lib.load()
     own = ctx is None
