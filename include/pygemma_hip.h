@@ -264,6 +264,26 @@ int pg_kinship_dev(pg_ctx *ctx, int64_t n, int64_t p_k, const float *Gt, int64_t
  * mirror, bit-symmetric).  K can go straight into pg_syevd_dev. */
 int pg_kinship_geno_dev(pg_ctx *ctx, int64_t n, int64_t p, const float *G, int64_t ldG, int standardize, float *K);
 
+/* ---- The same K accumulated over SNP batches (csrc/kinship.hip): host and device memory bounded at any p.
+ * acc: device buffer of pg_kinship_acc_bytes(n, pb) bytes for the largest batch pb used — an fp64 n x n accumulator (its first
+ *      8 n^2 bytes, zeroed by the caller before the first batch; lower triangle used) followed by the batch work area.
+ * pg_kinship_bed_acc_dev : pb packed .bed records (row stride ldb >= ceil(n/4) bytes), code convention and count_a1 of
+ *      pg_rotate_bed_dev; a missing call takes the mean of the called genotypes of its SNP; an all-missing SNP contributes zeros.
+ * pg_kinship_x_acc_dev   : an (n x pb) sample-major (snp_major = 0, row stride ldX >= pb) or (pb x n) SNP-major (ldX >= n) block of
+ *      dtype PG_DTYPE_*.  8-bit values and .bed codes go through the fp16 matrix pipe (exact operand, the other in two fp16 planes,
+ *      fp32 accumulation per batch); float blocks, and every block when the environment has PG_KINSHIP_FP32=1, through the fp32 syrk.
+ *      Per SNP: fp64 mean and population variance over all n samples after imputation; standardize != 0 centres and scales by 1/sd
+ *      (sd == 0 -> 1), else X X'.
+ * pg_kinship_finish_dev  : K = acc / p as float32 (n x n, row-major), both triangles, bit-symmetric; p = the total number of SNPs.
+ * Batches are summed in call order on the context's stream; the result depends only on the inputs and the batch boundaries. */
+enum { PG_DTYPE_INT8 = 0, PG_DTYPE_UINT8 = 1, PG_DTYPE_FLOAT32 = 2, PG_DTYPE_FLOAT64 = 3 };
+size_t pg_kinship_acc_bytes(int64_t n, int64_t pb);
+int pg_kinship_bed_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, int standardize,
+                           double *acc);
+int pg_kinship_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, int standardize,
+                         double *acc);
+int pg_kinship_finish_dev(pg_ctx *ctx, int64_t n, int64_t p, const double *acc, float *K);
+
 /* ---- lmm/lmm.py:124-125: K <- Z K Z' for the optional design matrix Z (n x q) of the random effect, K (q x q).  Z and K may each be
  * float32 or float64 (z_is_f64 / k_is_f64), row-major with row strides ldz / ldk, on the device; out = float32 (n x n, row stride ldo),
  * what lmm.py:127-128 hands to the eigensolver.  Two fp64-MFMA products and one rounding. */

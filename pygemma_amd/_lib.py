@@ -24,6 +24,7 @@ SYMBOLS = [
     "pg_comm_broadcast_dev", "pg_comm_allgather_dev", "pg_comm_allreduce_f64_dev", "pg_comm_barrier", "pg_comm_group_start",
     "pg_comm_group_end", "pgx_dgemm_dev", "pgx_sytrd_dev", "pgx_stedc_dev", "pgx_sb2_stage1_dev", "pgx_sb2_stage2_dev", "pgx_sb2_set_debug", "pg_kinship_geno_dev", "pg_assoc_lrt_dev", "pg_rotate_auto_dev", "pg_assoc_set_eval_trace", "pg_assoc_warm", "pg_rotate_auto_i8_dev",
     "pg_zkzt_dev", "pgx_dgemm_ex_dev", "pgx_ring_stamps", "pg_assoc_pheno_dev", "pg_assoc_pheno_warm", "pg_score_null_dev", "pg_score_dev",
+    "pg_kinship_acc_bytes", "pg_kinship_bed_acc_dev", "pg_kinship_x_acc_dev", "pg_kinship_finish_dev",
 ]
 
 
@@ -68,6 +69,14 @@ def load():
     L.pg_kinship_dev.argtypes = [vp, i64, i64, vp, i64, vp]
     L.pg_kinship_geno_dev.argtypes = [vp, i64, i64, vp, i64, i32, vp]
     L.pg_kinship_geno_dev.restype = i32
+    L.pg_kinship_acc_bytes.argtypes = [i64, i64]
+    L.pg_kinship_acc_bytes.restype = sz
+    L.pg_kinship_bed_acc_dev.argtypes = [vp, i64, i64, vp, i64, i32, i32, vp]
+    L.pg_kinship_bed_acc_dev.restype = i32
+    L.pg_kinship_x_acc_dev.argtypes = [vp, i64, i64, vp, i32, i64, i32, i32, vp]
+    L.pg_kinship_x_acc_dev.restype = i32
+    L.pg_kinship_finish_dev.argtypes = [vp, i64, i64, vp, vp]
+    L.pg_kinship_finish_dev.restype = i32
     L.pg_geno_prep_bytes.argtypes = [i64]
     L.pg_geno_prep_bytes.restype = sz
     L.pg_geno_work_bytes.argtypes = [i64, i64]

@@ -31,6 +31,7 @@ struct RotParams {
     int tiles_m, tiles_n;
     int lower;   // syrk mode (square output, X == U): only tiles on or below the diagonal are computed, the rest is mirrored
     const int *cond;   // pg_rotate_auto_dev: run only if (cond[0] & 2), i.e. the block holds a NaN/Inf (nullptr: always)
+    double *acc;       // rotate_acc_kernel: acc[row * ldx + col] += out for row >= col (syrk mode; Xr unused)
 };
 
 template <int VEC>
@@ -51,8 +52,9 @@ __device__ __forceinline__ float4 load4(const float *base, long long row, long l
     return v;
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256, 2) void rotate_kernel(RotParams rp)
+// ACC: the accumulating epilogue of the streamed kinship (lower triangle of an fp64 accumulator), a separate instantiation
+template <int VEC, bool ACC>
+__device__ __forceinline__ void rotate_body(RotParams rp)
 {
     __shared__ float As[2][RBK][RBM];
     __shared__ float Bs[2][RBK][RBN];
@@ -143,7 +145,9 @@ __global__ __launch_bounds__(256, 2) void rotate_kernel(RotParams rp)
 #pragma unroll
             for (int e = 0; e < 16; e++) {
                 const long long row = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (row < rp.p && col < rp.ldx) {
+                if constexpr (ACC) {
+                    if (row < rp.p && col < rp.ncol && row >= col) rp.acc[row * rp.ldx + col] += (double)acc[i][j][e];
+                } else if (row < rp.p && col < rp.ldx) {
                     const float v = rp.scale == 1.0f ? acc[i][j][e] : rp.scale * acc[i][j][e];
                     rp.Xr[row * rp.ldx + col] = v;
                     if (rp.lower && tn < tm && col < rp.ncol) rp.Xr[col * rp.ldx + row] = v;   // mirror of an off-diagonal tile
@@ -151,6 +155,11 @@ __global__ __launch_bounds__(256, 2) void rotate_kernel(RotParams rp)
             }
         }
 }
+
+template <int VEC>
+__global__ __launch_bounds__(256, 2) void rotate_kernel(RotParams rp) { rotate_body<VEC, false>(rp); }
+template <int VEC>
+__global__ __launch_bounds__(256, 2) void rotate_acc_kernel(RotParams rp) { rotate_body<VEC, true>(rp); }
 
 }  // namespace pg
 
@@ -176,6 +185,24 @@ static int launch_tn(pg_ctx *ctx, long long kdim, long long ncol, long long p, c
 }
 
 namespace pg {
+// acc (n x n fp64, row-major) += Zt' Zt on tiles on or below the diagonal, elements row >= col only: the fp32 path of the streamed
+// kinship (kinship.hip).  Zt: (kdim x ldz) SNP-major float32.
+int syrk_acc_fp32(pg_ctx *ctx, long long kdim, long long n, const float *Zt, long long ldz, double *acc)
+{
+    RotParams rp{};
+    rp.kdim = kdim; rp.ncol = n; rp.p = n; rp.ldx = n; rp.ldU = ldz; rp.ldX = ldz; rp.U = Zt; rp.X = Zt; rp.scale = 1.0f;
+    rp.tiles_m = rp.tiles_n = (int)((n + RBM - 1) / RBM);
+    rp.lower = 1;
+    rp.acc = acc;
+    const long long T = (long long)rp.tiles_m * (rp.tiles_m + 1) / 2;
+    PG_REQUIRE(T < (1LL << 31), "kinship: too many tiles");
+    const bool vec = (ldz % 4 == 0) && ((uintptr_t)Zt % 16 == 0);
+    if (vec) rotate_acc_kernel<4><<<dim3((unsigned)T), 256, 0, ctx->stream>>>(rp);
+    else rotate_acc_kernel<1><<<dim3((unsigned)T), 256, 0, ctx->stream>>>(rp);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
 int rotate_fp32_cond(pg_ctx *ctx, long long n, long long p, const float *U, long long ldU, const float *X, long long ldX, float *Xr,
                      long long ldx, const int *cond, int)
 {

@@ -337,6 +337,11 @@ struct GenoParams {
     const float *scale;         // {S, 1/S}
     const int *cond;            // device-side predication (pg_rotate_auto_dev): block flags of the detect pass, or nullptr
     int cmode;
+    // the streamed kinship's syrk (kin_geno_kernel, kinship.hip): Gt = the sample-major codes [n][ldk], Up = the planes of R [n][ldp],
+    // acc[row * n + col] += acc_tile / S - vk[col] for row >= col; K-tiles doubled (indicator pass) when kflag[0] != 0
+    double *acc;
+    const double *vk;
+    const int *kflag;
 };
 
 // LDS image of a 128-row x 64-k fp16 tile: plain 128-byte rows (what the LDS-DMA writes: a wave instruction fills
@@ -363,25 +368,36 @@ __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >>
 #ifndef PG_GENO_GRP
 #define PG_GENO_GRP 4
 #endif
-template <int MF>      // MFMA shape: 16 = v_mfma_f32_16x16x32_f16 (shipped), 32 = v_mfma_f32_32x32x16_f16 (measured alternative: see launch_geno_gemm)
-__global__ __launch_bounds__(512, 1) void rotate_geno_kernel(GenoParams gp)
+// KIN: the kinship syrk (tiles on or below the diagonal, K-tile count from kflag, accumulating fp64 epilogue), MF = 16 only
+template <int MF, bool KIN>      // MFMA shape: 16 = v_mfma_f32_16x16x32_f16 (shipped), 32 = v_mfma_f32_32x32x16_f16 (measured alternative: see launch_geno_gemm)
+__device__ __forceinline__ void geno_gemm_body(GenoParams gp)
 {
+    static_assert(!KIN || MF == 16, "the kinship epilogue is written for the 16 x 16 tiles");
     if (!run_cond(gp.cond, gp.cmode)) return;      // uniform over the grid: every wave leaves before any barrier
     constexpr int TBUF = 256 * 128;
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     unsigned char *const Bs = lds, *const As = lds + 3 * TBUF;
-    const int T = gp.tiles_m * gp.tiles_n;
+    const int T = KIN ? gp.tiles_m * (gp.tiles_m + 1) / 2 : gp.tiles_m * gp.tiles_n;
     const int b = blockIdx.x;
     const int q = T / 8, r = T % 8, xcd = b % 8;
     const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-    const int per_group = PG_GENO_GRP * gp.tiles_n;
-    const int grp = lid / per_group, first_m = grp * PG_GENO_GRP;
-    const int gsz = (gp.tiles_m - first_m) < PG_GENO_GRP ? (gp.tiles_m - first_m) : PG_GENO_GRP;
-    const int tm = first_m + (lid % per_group) % gsz, tn = (lid % per_group) / gsz;
+    int tm, tn;
+    if constexpr (KIN) {      // lid -> (tm, tn), tn <= tm, row-major over the lower triangle of the tile grid (rotate.hip's syrk map)
+        tm = (int)((sqrtf(8.0f * (float)lid + 1.0f) - 1.0f) * 0.5f);
+        while (tm * (tm + 1) / 2 > lid) tm--;
+        while ((tm + 1) * (tm + 2) / 2 <= lid) tm++;
+        tn = lid - tm * (tm + 1) / 2;
+    } else {
+        const int per_group = PG_GENO_GRP * gp.tiles_n;
+        const int grp = lid / per_group, first_m = grp * PG_GENO_GRP;
+        const int gsz = (gp.tiles_m - first_m) < PG_GENO_GRP ? (gp.tiles_m - first_m) : PG_GENO_GRP;
+        tm = first_m + (lid % per_group) % gsz; tn = (lid % per_group) / gsz;
+    }
     const long long m0 = (long long)tm * 256, n0 = (long long)tn * 256;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wm = wave >> 1, wn = wave & 1;          // 4 x 2 waves, each 64 (SNPs) x 128 (eigen indices)
-    const int KT2 = 2 * gp.KT;
+    const int KT = KIN ? (gp.kflag[0] ? 2 * gp.KT : gp.KT) : gp.KT;     // KIN: + the indicator K-tiles when the batch has missing calls
+    const int KT2 = 2 * KT;
 
     // 128 accumulator registers either way: 4 x 8 tiles of 16 x 16 (4 floats per lane) or 2 x 4 tiles of 32 x 32 (16 per lane)
     floatx4 acc[MF == 16 ? 4 : 1][MF == 16 ? 8 : 1];
@@ -436,14 +452,14 @@ __global__ __launch_bounds__(512, 1) void rotate_geno_kernel(GenoParams gp)
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     } else {
         dmaA(0, 0); dmaA(0, 1);
-        if (gp.KT > 1) { dmaA(1, 0); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
+        if (KT > 1) { dmaA(1, 0); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
     if (late) __builtin_amdgcn_s_barrier();
     int b0 = 0;
     halfx8 fa[2][4];
-    for (int ktile = 0; ktile < gp.KT; ktile++) {
+    for (int ktile = 0; ktile < KT; ktile++) {
       const unsigned char *Acur = As + (ktile & 1) * TBUF;
 #pragma unroll
       for (int pl = 0; pl < 2; pl++) {
@@ -453,8 +469,8 @@ __global__ __launch_bounds__(512, 1) void rotate_geno_kernel(GenoParams gp)
         bool issued = false;
         // ---------------- memory phase
         if (late) { if (kt + 2 < KT2) { dmaB(kt + 2, b2); issued = true; } }
-        else if (pl == 0) { if (ktile + 1 < gp.KT) { dmaA(ktile + 1, 1); issued = true; } }   // second half of K-tile T+1
-        else { if (ktile + 2 < gp.KT) { dmaA(ktile + 2, 0); issued = true; } }              // first half of K-tile T+2
+        else if (pl == 0) { if (ktile + 1 < KT) { dmaA(ktile + 1, 1); issued = true; } }   // second half of K-tile T+1
+        else { if (ktile + 2 < KT) { dmaA(ktile + 2, 0); issued = true; } }              // first half of K-tile T+2
         halfx8 fb[8];
         const int chunk0 = (MF == 16) ? (lane >> 4) : (lane >> 5);
         if (MF == 16) {
@@ -552,6 +568,25 @@ __global__ __launch_bounds__(512, 1) void rotate_geno_kernel(GenoParams gp)
     }
     if (!late) __builtin_amdgcn_s_barrier();
     const double invS = (double)gp.scale[1];
+    if constexpr (KIN) {      // fp64 accumulator, elements on or below the diagonal: acc += a / S - vk[col] (the rank-1 shift term)
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const long long col = n0 + wn * 128 + j * 16 + (lane & 15);
+                if (col >= gp.n) continue;
+                const double vc = gp.vk[col];
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const long long row = m0 + wm * 64 + i * 16 + 4 * (lane >> 4) + e;
+                    if (row < gp.n && row >= col) {
+                        double *dst = gp.acc + row * gp.n + col;
+                        *dst += fma((double)acc[MF == 16 ? i : 0][MF == 16 ? j : 0][e], invS, -vc);
+                    }
+                }
+            }
+        return;
+    }
     const bool accum = gp.v0 == nullptr;
     auto put = [&](long long row, long long col, double ck, float a) {
         if (row < gp.p && col < gp.ldx) {
@@ -584,6 +619,10 @@ __global__ __launch_bounds__(512, 1) void rotate_geno_kernel(GenoParams gp)
             }
     }
 }
+
+template <int MF>
+__global__ __launch_bounds__(512, 1) void rotate_geno_kernel(GenoParams gp) { geno_gemm_body<MF, false>(gp); }
+__global__ __launch_bounds__(512, 1) void kin_geno_kernel(GenoParams gp) { geno_gemm_body<16, true>(gp); }
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -1222,3 +1261,23 @@ extern "C" int pgx_geno_stamps(long long *out192)
     return hipMemcpyFromSymbol(out192, HIP_SYMBOL(pg::g_geno_stamps), sizeof(long long) * 192) == hipSuccess ? 0 : -1;
 }
 #endif
+
+namespace pg {
+// The streamed kinship's fp16 syrk (kinship.hip): acc (n x n fp64) += (A B' / S - 1 vk') on and below the diagonal.  A: sample-major
+// codes [n][ldA] (kts K-tiles of 64 SNPs, then kts indicator K-tiles), B: [n][ldB] the two planes of S*R per K-tile (then of S*mu*R).
+int kin_geno_gemm(pg_ctx *ctx, long long n, int kts, const unsigned short *A, long long ldA, const unsigned short *B, long long ldB,
+                  const float *scale, const double *vk, const int *kflag, double *acc)
+{
+    constexpr int WLDS = 5 * 256 * 128;
+    GenoParams gp{};
+    gp.n = n; gp.p = n; gp.ldk = ldA; gp.ldp = ldB; gp.Gt = A; gp.Up = B; gp.scale = scale;
+    gp.acc = acc; gp.vk = vk; gp.kflag = kflag;
+    gp.tiles_m = gp.tiles_n = (int)((n + 255) / 256); gp.KT = kts;
+    const long long T = (long long)gp.tiles_m * (gp.tiles_m + 1) / 2;
+    PG_REQUIRE(T < (1LL << 31), "kinship: too many tiles");
+    PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&kin_geno_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WLDS));
+    kin_geno_kernel<<<dim3((unsigned)T), 512, WLDS, ctx->stream>>>(gp);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+}  // namespace pg

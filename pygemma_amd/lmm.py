@@ -488,11 +488,38 @@ def _make_comms(L, ndev):
     return [_Comm(C.c_void_p(outs[g]), ctxs[g]) for g in range(ndev)]
 
 
-def kinship(G, standardize=True, device=0):
+def kinship(G, standardize=True, device=0, *, snp_batch=None):
     """K = Z Z' / p from the (n, p) genotype matrix G on the GPU (the step before the path in the reference's callers:
     experiments/animal_gwas/run_gwas.py:46-56, tests/test_pygemma.py:184-192): columns centred and divided by their
     standard deviation (population, ddof=0; sd == 0 -> 1) when `standardize`, then a lower-triangle syrk on the MFMA pipe.
-    Returns the (n, n) float32 matrix (both triangles)."""
+    Returns the (n, n) float32 matrix (both triangles, bit-symmetric), ready for `pygemma`.
+
+    G may also be a `PackedBed`, and an array may be streamed with `snp_batch`: then SNP batches of that many columns travel to
+    the device one after the other (host and device memory bounded at any p) and K is accumulated there in fp64
+    (DESIGN §4.7).  The streamed path takes a PackedBed (always; `snp_batch` None picks the batch from n and the free device
+    memory) and int8, uint8, float32 or float64 arrays, sample-major (C order) or SNP-major (Fortran order), pinned or
+    pageable, without a host copy or cast of the whole matrix.  .bed codes and 8-bit values go through the fp16 matrix pipe,
+    float blocks through the fp32 syrk (PG_KINSHIP_FP32=1 sends every block there).  A missing .bed call takes the mean of the
+    called genotypes of its SNP, so K equals kinship(G.to_float(impute=True)) up to rounding; an all-missing SNP, where
+    to_float gives NaN, is treated like a monomorphic one: it contributes zeros and still counts in p.
+    With an array and `snp_batch` None, the whole float32 matrix is uploaded and handled at once (the original path)."""
+    if snp_batch is not None and (isinstance(snp_batch, bool) or not isinstance(snp_batch, (int, np.integer)) or snp_batch < 1):
+        raise ValueError(f"snp_batch must be a positive integer, not {snp_batch!r}")
+    if isinstance(G, PackedBed):
+        if G.n < 1 or G.p < 1:
+            raise ValueError(f"kinship needs at least one sample and one SNP: the PackedBed holds n={G.n}, p={G.p}")
+        return _kinship_stream(G, bool(standardize), device, snp_batch)
+    if snp_batch is not None:
+        G = np.asarray(G)
+        if G.ndim != 2:
+            raise ValueError(f"G must be a 2-D (n, p) array, not {G.ndim}-D")
+        if G.dtype not in _KIN_DTYPES:
+            raise ValueError(f"streamed kinship takes int8, uint8, float32 or float64 genotypes, not {G.dtype}")
+        if G.shape[0] < 1 or G.shape[1] < 1:
+            raise ValueError(f"kinship needs at least one sample and one SNP: G is {G.shape}")
+        if not (G.flags.c_contiguous or G.flags.f_contiguous):
+            G = np.ascontiguousarray(G)
+        return _kinship_stream(G, bool(standardize), device, snp_batch)
     L = _lib.load()
     G = np.ascontiguousarray(G, np.float32)
     n, p = G.shape
@@ -502,6 +529,114 @@ def kinship(G, standardize=True, device=0):
         _lib.check(L.pg_kinship_geno_dev(ctx.handle, n, p, dG.ptr, p, int(bool(standardize)), dK.ptr), "pg_kinship_geno_dev")
         ctx.sync()
         return dK.download((n, n), np.float32)
+
+
+_KIN_DTYPES = {np.dtype(np.int8): 0, np.dtype(np.uint8): 1, np.dtype(np.float32): 2, np.dtype(np.float64): 3}   # PG_DTYPE_*
+# SNPs per batch by default: the fp64 read-modify-write of the accumulator (8 n^2 bytes per batch) against the batch's syrk
+# (2 n^2 pb fp16 flops on and below the diagonal) costs ~1 000 / pb of the batch at 5 TB/s and 1.2 PF: 6 % at 16 384
+_KIN_BATCH = 16384
+
+
+def _kinship_stream(G, standardize, device, snp_batch):
+    """The streamed kinship: SNP batches through pg_kinship_{bed,x}_acc_dev into one fp64 accumulator, then pg_kinship_finish_dev.
+    Uploads run on a second stream into two device slots, one batch ahead of the kernels, ordered by events."""
+    L = _lib.load()
+    packed = isinstance(G, PackedBed)
+    n, p = (G.n, G.p) if packed else G.shape
+    if packed:
+        src_arr, row_bytes, snp_major, esz = G.data, G.data.shape[1], True, 1
+    else:
+        src_arr, esz = G, G.itemsize
+        snp_major = G.flags.f_contiguous and not G.flags.c_contiguous
+        row_bytes = n * esz
+    direct = _lib.is_pinned(src_arr) and (not packed or src_arr.flags.c_contiguous)
+    with _lib.Context(device) as ctx, _lib.Context(device) as up:
+        free, _total = ctx.mem_info()
+
+        def need(pb):
+            return int(L.pg_kinship_acc_bytes(n, pb)) + 4 * n * n + 2 * pb * row_bytes
+
+        if snp_batch is None:
+            pb = min(p, _KIN_BATCH)
+            while pb > 64 and need(pb) > 0.9 * free:
+                pb = max(64, pb // 2)
+        else:
+            pb = min(p, int(snp_batch))
+        if need(pb) > free:
+            raise _lib.PgError(f"kinship: n={n}, snp_batch={pb} needs {need(pb) / 2**30:.2f} GiB of device memory (fp64 accumulator "
+                               f"8 n^2, K 4 n^2, batch buffers), {free / 2**30:.2f} GiB free on GPU {device}")
+        dacc = ctx.alloc(L.pg_kinship_acc_bytes(n, pb))
+        dK = ctx.alloc(4 * n * n)
+        slots = [ctx.alloc(pb * row_bytes) for _ in range(2)]
+        staging, events = [], []
+        try:
+            for _ in range(0 if direct else 2):
+                h = C.c_void_p()
+                _lib.check(L.pg_host_alloc(up.handle, pb * row_bytes, C.byref(h)), "pg_host_alloc")
+                staging.append(h.value)
+            for c_ in (up, up, ctx, ctx):
+                ev = C.c_void_p()
+                _lib.check(L.pg_event_create(c_.handle, C.byref(ev)), "pg_event_create")
+                events.append(ev)
+            ev_up, ev_done = events[:2], events[2:]
+            _lib.check(L.pg_memset(ctx.handle, dacc.ptr, 0, 8 * n * n), "pg_memset")
+            batches = [(s, min(s + pb, p)) for s in range(0, p, pb)]
+            base = src_arr.ctypes.data
+
+            def upload(b):
+                s, e = batches[b]
+                k, w = b % 2, e - s
+                if b >= 2:
+                    _lib.check(L.pg_stream_wait_event(up.handle, ev_done[k]), "pg_stream_wait_event")   # batch b-2 is done with the slot
+                if packed and not src_arr.flags.c_contiguous:
+                    rec = np.ascontiguousarray(src_arr[s:e])
+                    if b >= 2:
+                        _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")
+                    C.memmove(staging[k], rec.ctypes.data, rec.nbytes)
+                    _lib.check(L.pg_memcpy_h2d_async(up.handle, slots[k].ptr, staging[k], rec.nbytes), "pg_memcpy_h2d_async")
+                elif snp_major:        # SNP records [s, e): contiguous bytes
+                    src = base + s * row_bytes
+                    if direct:
+                        _lib.check(L.pg_memcpy_h2d_async(up.handle, slots[k].ptr, src, w * row_bytes), "pg_memcpy_h2d_async")
+                    else:
+                        if b >= 2:
+                            _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")    # the DMA of batch b-2 has left the staging
+                        _lib.check(L.pg_stage_rows(staging[k], row_bytes, src, row_bytes, row_bytes, w, _STAGE_THREADS), "pg_stage_rows")
+                        _lib.check(L.pg_memcpy_h2d_async(up.handle, slots[k].ptr, staging[k], w * row_bytes), "pg_memcpy_h2d_async")
+                else:                  # sample-major: the column window [s, e) of every row, packed to row stride w
+                    src = base + s * esz
+                    if direct:
+                        _lib.check(L.pg_memcpy2d_h2d_async(up.handle, slots[k].ptr, w * esz, src, p * esz, w * esz, n), "pg_memcpy2d_h2d_async")
+                    else:
+                        if b >= 2:
+                            _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")
+                        _lib.check(L.pg_stage_rows(staging[k], w * esz, src, p * esz, w * esz, n, _STAGE_THREADS), "pg_stage_rows")
+                        _lib.check(L.pg_memcpy_h2d_async(up.handle, slots[k].ptr, staging[k], n * w * esz), "pg_memcpy_h2d_async")
+                _lib.check(L.pg_event_record(up.handle, ev_up[k]), "pg_event_record")
+
+            upload(0)
+            for b, (s, e) in enumerate(batches):
+                k, w = b % 2, e - s
+                _lib.check(L.pg_stream_wait_event(ctx.handle, ev_up[k]), "pg_stream_wait_event")
+                if packed:
+                    _lib.check(L.pg_kinship_bed_acc_dev(ctx.handle, n, w, slots[k].ptr, row_bytes, int(G.count_A1), int(standardize), dacc.ptr),
+                               "pg_kinship_bed_acc_dev")
+                else:
+                    _lib.check(L.pg_kinship_x_acc_dev(ctx.handle, n, w, slots[k].ptr, _KIN_DTYPES[G.dtype], n if snp_major else w, int(snp_major),
+                                                      int(standardize), dacc.ptr), "pg_kinship_x_acc_dev")
+                _lib.check(L.pg_event_record(ctx.handle, ev_done[k]), "pg_event_record")
+                if b + 1 < len(batches):
+                    upload(b + 1)      # overlaps the kernels of batch b
+            _lib.check(L.pg_kinship_finish_dev(ctx.handle, n, p, dacc.ptr, dK.ptr), "pg_kinship_finish_dev")
+            ctx.sync()
+            return dK.download((n, n), np.float32)
+        finally:
+            up.sync()
+            ctx.sync()
+            for ev in events:
+                L.pg_event_destroy(up.handle, ev)
+            for h in staging:
+                L.pg_host_free(up.handle, h)
 
 
 def _zkzt(L, Z, K):
