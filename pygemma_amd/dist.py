@@ -164,14 +164,19 @@ def gather_result_rows(comm, res_ptr, all_ptr, cols):
     comm.allgather(res_ptr, all_ptr, 32 * int(cols))
 
 
+def result_columns(host_bytes, cols):
+    """Views of `cols` 32-byte result rows [F | p | beta | se | tau | lambda] (each field `cols` values, one after the other):
+    F_wald and p_wald float64, beta, se_beta, tau and lambda float32."""
+    b = np.frombuffer(host_bytes, np.uint8, 32 * cols)
+    f4 = b[16 * cols:32 * cols].view(np.float32).reshape(4, cols)
+    return {"beta": f4[0], "se_beta": f4[1], "tau": f4[2], "lambda": f4[3],
+            "F_wald": b[:8 * cols].view(np.float64), "p_wald": b[8 * cols:16 * cols].view(np.float64)}
+
+
 def unpack_block(host_bytes, cols, count):
     """One rank's block (cols rows, `count` of them real) -> dict of the six columns."""
-    b = np.frombuffer(host_bytes, np.uint8, 32 * cols)
-    F = b[:8 * cols].view(np.float64)[:count]
-    pv = b[8 * cols:16 * cols].view(np.float64)[:count]
-    f4 = b[16 * cols:32 * cols].view(np.float32).reshape(4, cols)[:, :count]
-    return {"beta": f4[0].copy(), "se_beta": f4[1].copy(), "tau": f4[2].copy(), "lambda": f4[3].astype(np.float64),
-            "F_wald": F.copy(), "p_wald": pv.copy()}
+    v = result_columns(host_bytes, cols)
+    return {k: a[:count].astype(np.float64) if k == "lambda" else a[:count].copy() for k, a in v.items()}
 
 
 def pack_block(res, cols):

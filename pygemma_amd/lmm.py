@@ -20,18 +20,19 @@ result rows come back through a pinned buffer.  With several GPUs the eigenvecto
 RCCL broadcast over xGMI (pg_comm_*; no PyTorch).
 There is no CPU fallback: without the HIP library or a GPU this raises.
 """
-import contextlib
 import ctypes as C
 import json
 import os
 import threading
 import time
 import zlib
+from collections import namedtuple
+from types import SimpleNamespace
 
 import numpy as np
 import pandas as pd
 
-from . import _lib
+from . import _lib, dist
 from ._lib import pin, pinned_empty     # noqa: F401  (re-exported: how a caller hands over pinned inputs)
 from .bed import PackedBed
 from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_restricted, newton, the *_overload scalars)
@@ -42,7 +43,6 @@ __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "SampleIter", "pinned_em
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
 _WORKERS = 2             # host threads (each with its own stream and buffers) per GPU
-_SERIAL_KERNELS = False  # True: the workers of a GPU take turns on its compute units (measured: no gain for float32 X, 8 % slower for int8 X)
 _BATCH_MIN = 8192        # ... and at least, while the block is cut into up to _BATCH_COUNT batches: the first batch's DMA and the
 _BATCH_COUNT = 12        # last batch's kernels are the part of the loop that does not overlap (measured at p = 100 000: 4 batches
                          # 0.149-0.172 s, 8: 0.116, 12: 0.112, 16: 0.112 — tools/ab_stream_batch.py)
@@ -118,25 +118,50 @@ def _block_fingerprint(X, s, e):
     return _crc(X[rows, s:e])
 
 
-class _Staging:
-    """Pinned host buffers of one worker: the raw batch on its way in (unless X itself is pinned) and the result rows on
-    their way out."""
+class _Pinned:
+    """Pinned host buffers (hipHostMalloc through ctx), one per size in `sizes` (`.bufs`), freed together by close()."""
 
-    def __init__(self, ctx, L, in_bytes, out_bytes):
-        self.ctx, self.L = ctx, L
-        self.inp = self._alloc(in_bytes) if in_bytes else None
-        self.out = self._alloc(out_bytes)
-
-    def _alloc(self, nbytes):
-        p = C.c_void_p()
-        _lib.check(self.L.pg_host_alloc(self.ctx.handle, int(nbytes), C.byref(p)), "pg_host_alloc")
-        return p.value
+    def __init__(self, ctx, *sizes):
+        self.ctx, self.bufs = ctx, []
+        try:
+            for nbytes in sizes:
+                p = C.c_void_p()
+                _lib.check(_lib.load().pg_host_alloc(ctx.handle, int(nbytes), C.byref(p)), "pg_host_alloc")
+                self.bufs.append(p.value)
+        except BaseException:
+            self.close()
+            raise
 
     def close(self):
-        for q in (self.inp, self.out):
-            if q:
-                self.L.pg_host_free(self.ctx.handle, q)
-        self.inp = self.out = None
+        for q in self.bufs:
+            _lib.load().pg_host_free(self.ctx.handle, q)
+        self.bufs = []
+
+
+def _put_window(ctx, src, s, e, dst, dpitch=None, staging=None, threads=_STAGE_THREADS):
+    """SNPs [s, e) of a host source -> device address `dst`, in ONE DMA on ctx's stream.
+    `src` is an (n, p) array in C order (sample-major: n rows of the window's e - s values, landing `dpitch` bytes apart), or one
+    in F order or a PackedBed (SNP-major: e - s contiguous rows, one per SNP, landing back to back, or `dpitch` apart through a
+    2-D DMA when it is given).  Without `staging` src is pinned and the DMA reads it.  Otherwise `threads` copy threads first
+    gather the window into the pinned buffer `staging`: sample-major rows at `dpitch` (then the DMA is flat), SNP-major rows back
+    to back.  Waiting until `staging` or `dst` is free again is the caller's business."""
+    L = _lib.load()
+    if isinstance(src, PackedBed):
+        rec = np.ascontiguousarray(src.data[s:e])      # a view of the records, unless they are strided
+        snp_major, ptr, spitch, width, rows = True, rec.ctypes.data, rec.shape[1], rec.shape[1], e - s
+    elif src.flags.f_contiguous and not src.flags.c_contiguous:
+        width = src.shape[0] * src.itemsize
+        snp_major, ptr, spitch, rows = True, src.ctypes.data + s * width, width, e - s
+    else:
+        snp_major, ptr, spitch, width, rows = False, src.ctypes.data + s * src.itemsize, src.strides[0], (e - s) * src.itemsize, src.shape[0]
+    if staging is not None:
+        sp = width if snp_major else (dpitch or width)
+        _lib.check(L.pg_stage_rows(staging, sp, ptr, spitch, width, rows, threads), "pg_stage_rows")
+        ptr, spitch = staging, sp
+    if dpitch is None or (staging is not None and not snp_major):     # the rows lie as they will on the device
+        _lib.check(L.pg_memcpy_h2d_async(ctx.handle, dst, ptr, rows * (dpitch or width)), "pg_memcpy_h2d_async")
+    else:
+        _lib.check(L.pg_memcpy2d_h2d_async(ctx.handle, dst, dpitch, ptr, spitch, width, rows), "pg_memcpy2d_h2d_async")
 
 
 def _batch_geometry(n, a, b):
@@ -199,7 +224,7 @@ class _Prefetch:
 
     def _run(self, g):
         try:
-            n, esz, p = self.n, self.esz, self.X.shape[1]
+            n, esz = self.n, self.esz
             ctx = self.ctxs[g]
             batches, big, per, ldX = self.plans[g]
             done = 0
@@ -207,8 +232,7 @@ class _Prefetch:
                 if self.stop:
                     break
                 dst = big.ptr + k * per
-                _lib.check(self.L.pg_memcpy2d_h2d_async(ctx.handle, dst, ldX * esz, self.X.ctypes.data + esz * s, p * esz, (e - s) * esz, n),
-                           "pg_memcpy2d_h2d_async")
+                _put_window(ctx, self.X, s, e, dst, ldX * esz)
                 ctx.sync()                       # a batch is offered only once it has landed
                 with self.lock:
                     self.ready[g][(s, e)] = _View(dst)
@@ -235,16 +259,96 @@ class _Prefetch:
         self.ctxs = []
 
 
-def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out, errs, verbose, ckpt=None, stats=None, pre=None,
-               npheno=0, lam0=None):
-    """One GPU: SNP columns [a,b) of X through (rotate | transpose) -> assoc, in batches.  With `npheno` > 0, yr holds that many
-    rotated phenotypes (npheno, n) and every batch, transported and rotated once, goes through pg_assoc_pheno_dev for all of them.
-    With `lam0` (the null model's float32 ML lambda, the same for every GPU) every batch goes through pg_score_dev instead, into the
-    same result rows [F | p | beta | se | tau | lambda].  Two host threads per GPU, each with
-    its own stream, device buffers and pinned staging, take batches from a shared list, so that the host->device DMA of one
-    batch overlaps the kernels of the other.  `dU`: GPU 0's resident eigenvectors (device 0) or None; with a communicator the
-    other GPUs receive them by RCCL broadcast.  With `ckpt` every finished batch is written to disk (and batches found there,
-    with a matching fingerprint of the raw block, are not redone)."""
+# What one kind of scan does with a batch of rotated SNPs (_scan_mode builds it once per call): its result columns in output order
+# (also those of a checkpoint part), result bytes per SNP, warm(ctx, pb_max) before a worker's first batch (or None),
+# launch(ctx, dev, pb, dXr, r0) of a batch's kernels (dev = (d, W, y) on that GPU, result rows at r0) and decode(host bytes, out,
+# s, e) of a batch's result rows into out[col][..., s:e]
+_Mode = namedtuple("_Mode", "cols nout warm launch decode")
+
+
+def _scan_mode(L, n, c, grid, lrt, npheno, lam0):
+    """The Wald scan (with `lrt` plus the likelihood-ratio columns), the scan of `npheno` > 0 phenotypes, or the score scan at the
+    null model's float32 ML lambda `lam0` (the same for every GPU).  Each writes the 32-byte rows [F | p | beta | se | tau | lambda]
+    of dist.result_columns, for npheno phenotype-major rows of pb SNPs with npheno; lrt appends [l_alt | l_null | D_lrt | p_lrt]
+    in float64."""
+    ldx = (n + 63) // 64 * 64
+    t = npheno or 1
+
+    def rows(r0, m):      # the fields of m result rows at r0 in the kernels' argument order: beta, se, tau, lambda, F, p
+        return r0 + 16 * m, r0 + 20 * m, r0 + 24 * m, r0 + 28 * m, r0, r0 + 8 * m
+
+    warm = None
+    if npheno:
+        def warm(ctx, pb_max):
+            _lib.check(L.pg_assoc_pheno_warm(ctx.handle, n, c, npheno, pb_max), "pg_assoc_pheno_warm")
+
+        def launch(ctx, dev, pb, dXr, r0):
+            _lib.check(L.pg_assoc_pheno_dev(ctx.handle, n, c, pb, npheno, *dev, n, dXr, ldx, int(grid), *rows(r0, npheno * pb), None),
+                       "pg_assoc_pheno_dev")
+    elif lam0 is not None:
+        def launch(ctx, dev, pb, dXr, r0):
+            _lib.check(L.pg_score_dev(ctx.handle, n, c, pb, *dev, float(lam0), dXr, ldx, *rows(r0, pb)), "pg_score_dev")
+    else:
+        def warm(ctx, pb_max):      # the first batch's kernels then queue without a host stall
+            _lib.check(L.pg_assoc_warm(ctx.handle, n, c), "pg_assoc_warm")
+
+        def launch(ctx, dev, pb, dXr, r0):
+            if lrt:
+                _lib.check(L.pg_assoc_lrt_dev(ctx.handle, n, c, pb, *dev, dXr, ldx, int(grid), *rows(r0, pb),
+                                              r0 + 32 * pb, r0 + 40 * pb, r0 + 48 * pb, r0 + 56 * pb), "pg_assoc_lrt_dev")
+            else:
+                _lib.check(L.pg_assoc_dev(ctx.handle, n, c, pb, *dev, dXr, ldx, int(grid), *rows(r0, pb), None), "pg_assoc_dev")
+
+    def decode(hb, out, s, e):
+        pb = e - s
+        for col, v in dist.result_columns(hb, t * pb).items():
+            out[col][..., s:e] = v.reshape(npheno, pb) if npheno else v
+        if lrt:
+            LR = np.frombuffer(hb, np.float64, 4 * pb, 32 * pb).reshape(4, pb)
+            for k, col in enumerate(_LRT_COLS):
+                out[col][s:e] = LR[k]
+
+    return _Mode(_COLS + (_LRT_COLS if lrt else ()), 32 * t + (32 if lrt else 0), warm, launch, decode)
+
+
+# The per-call invariants every GPU's block of a scan reads: eigenvalues d, rotated covariates Wr (n, c), rotated phenotype yr ((n,),
+# or (npheno, n) phenotype-major rows), X as _scan leaves it, the _Mode, the checkpoint directory, the stats dict, the _Prefetch
+# (each or None), the result columns `out` (filled in place) and `errs`, where the block and worker threads leave their exceptions
+_Job = namedtuple("_Job", "n c d Wr yr X grid eigen mode ckpt stats pre verbose out errs")
+
+
+def _restore(job, device, a, b, pb_max):
+    """The batches of [a, b) still to do; those with a checkpoint part are read back into job.out instead."""
+    todo = []
+    for s in range(a, b, pb_max):
+        e = min(s + pb_max, b)
+        part = _part_path(job.ckpt, s, e) if job.ckpt else None
+        if part is None or not os.path.exists(part):
+            todo.append((s, e))
+            continue
+        with np.load(part) as z:
+            if "fingerprint" not in z.files or int(z["fingerprint"]) != _block_fingerprint(job.X, s, e):
+                raise ValueError(f"checkpoint part {part} was computed from different genotypes "
+                                 f"(fingerprint of SNPs [{s},{e}) differs): refusing to mix runs")
+            for col in job.mode.cols:
+                job.out[col][s:e] = z[col]
+        _log(job.verbose, f"GPU {device}: SNPs [{s},{e}) restored from {job.ckpt}")
+    return todo
+
+
+def _save_part(job, s, e):
+    tmp = _part_path(job.ckpt, s, e) + ".tmp.npz"
+    np.savez(tmp, fingerprint=np.int64(_block_fingerprint(job.X, s, e)), **{col: job.out[col][s:e] for col in job.mode.cols})
+    os.replace(tmp, _part_path(job.ckpt, s, e))
+
+
+def _run_block(job, device, a, b, dU, comm):
+    """One GPU: SNP columns [a,b) of X through (rotate | transpose) -> the kernels of job.mode, in batches.  Two host threads per
+    GPU, each with its own stream, device buffers and pinned staging, take batches from a shared list, so that the host->device
+    DMA of one batch overlaps the kernels of the other.  `dU`: GPU 0's resident eigenvectors (device 0) or None; with a
+    communicator the other GPUs receive them by RCCL broadcast.  With job.ckpt every finished batch is written to disk (and
+    batches found there, with a matching fingerprint of the raw block, are not redone)."""
+    n, X, eigen, stats, verbose = job.n, job.X, job.eigen, job.stats, job.verbose
     try:
         L = _lib.load()
         ctx0 = comm.ctx if comm is not None else _lib.Context(device)
@@ -260,7 +364,7 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
                 _lib.check(L.pg_comm_broadcast_dev(comm.handle, dU.ptr, n * n * 4, 0), "pg_comm_broadcast_dev")
                 ctx0.sync()
                 _log(verbose, f"GPU {device}: U ({n * n * 4 / 1e9:.2f} GB) broadcast over RCCL in {time.time() - t0:.3f} s")
-            dd, dW, dy = ctx0.to_device(d), ctx0.to_device(Wr), ctx0.to_device(yr)
+            dev = tuple(ctx0.to_device(v).ptr for v in (job.d, job.Wr, job.yr))
             if eigen:
                 # genotype fast path of the rotation (<= 3 equally spaced values per column), fp32 MFMA otherwise
                 dprep = ctx0.alloc(L.pg_geno_prep_bytes(n))
@@ -273,27 +377,59 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
             esz = 1 if x8 else (8 if x64 else 4)
             pb_max, ldX = _batch_geometry(n, a, b)
             bpr = (n + 3) // 4
-            p = X.shape[1]
             direct = (not packed) and _lib.is_pinned(X)        # X itself is page-locked: DMA straight out of it
             snp_major = (not packed) and X.flags.f_contiguous and not X.flags.c_contiguous     # (float32 only: pygemma() sees to it)
-            nout = 32 * npheno if npheno else 32 + (32 if lrt else 0)   # result bytes per SNP
-            todo = []
-            for s in range(a, b, pb_max):
-                e = min(s + pb_max, b)
-                if ckpt and os.path.exists(_part_path(ckpt, s, e)):
-                    with np.load(_part_path(ckpt, s, e)) as z:
-                        if "fingerprint" not in z.files or int(z["fingerprint"]) != _block_fingerprint(X, s, e):
-                            raise ValueError(f"checkpoint part {_part_path(ckpt, s, e)} was computed from different genotypes "
-                                             f"(fingerprint of SNPs [{s},{e}) differs): refusing to mix runs")
-                        for col in _COLS + (_LRT_COLS if lrt else ()):
-                            out[col][s:e] = z[col]
-                    _log(verbose, f"GPU {device}: SNPs [{s},{e}) restored from {ckpt}")
-                else:
-                    todo.append((s, e))
+            nout = job.mode.nout
+            todo = _restore(job, device, a, b, pb_max)
             lock = threading.Lock()
-            gpu = threading.Lock() if _SERIAL_KERNELS else contextlib.nullcontext()   # one batch's kernels at a time; the other worker's DMA runs under them
             if stats is not None:
                 stats["setup_s"] = max(stats.get("setup_s", 0.0), time.time() - t_blk)
+
+            def batch(ctx, w, s, e):
+                """SNPs [s, e) on this worker's stream up to their result rows in w.out; returns (t_dma, prefetched)."""
+                pb = e - s
+                # ---- the raw block travels to the device (or landed there while the eigensolver ran); dXc: where it is
+                dXc = job.pre.take(device, s, e) if job.pre is not None else None
+                prefetched = dXc is not None
+                if not prefetched:
+                    dXc = w.X
+                    if packed:       # SNP records [s, e) of the .bed image, staged by one thread
+                        _put_window(ctx, X, s, e, w.X.ptr, staging=w.inp, threads=1)
+                    elif snp_major:  # SNPs [s, e) are pb contiguous rows of n floats
+                        dst, dpitch = (w.T.ptr, 4 * n) if eigen else (w.Xr.ptr, 4 * ldx)     # eigen=False: already the layout the scan reads
+                        _put_window(ctx, X, s, e, dst, dpitch, w.inp)
+                        if eigen:    # (pb x n) -> (n x ldX): the transposition kernel with the roles of n and p exchanged
+                            _lib.check(L.pg_transpose_dev(ctx.handle, pb, n, w.T.ptr, n, w.X.ptr, ldX), "pg_transpose_dev")
+                    else:            # the column window [s, e) of every sample row, at row pitch ldX
+                        _put_window(ctx, X, s, e, w.X.ptr, ldX * esz, w.inp)
+                t_dma = time.time()
+                # ---- rotation: decode + impute + rotate for .bed records; otherwise the path is chosen on the device
+                if packed:
+                    _lib.check(L.pg_rotate_bed_dev(ctx.handle, n, pb, dprep.ptr, w.X.ptr, bpr, int(X.count_A1), w.Xr.ptr, ldx,
+                                                   w.work.ptr), "pg_rotate_bed_dev")
+                elif x64:
+                    is_geno = C.c_int(0)
+                    _lib.check(L.pg_rotate_geno_f64_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, ldX, w.Xr.ptr, ldx, w.work.ptr,
+                                                        C.byref(is_geno)), "pg_rotate_geno_f64_dev")
+                    if not is_geno.value:
+                        w.Xf = w.Xf or ctx.alloc(n * ldX * 4)      # float32 image of a block that does not qualify for the genotype path
+                        _lib.check(L.pg_cast_f64_f32_dev(ctx.handle, n, pb, dXc.ptr, ldX, w.Xf.ptr, ldX), "pg_cast_f64_f32_dev")
+                        _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, w.Xf.ptr, ldX, w.Xr.ptr, ldx), "pg_rotate_dev")
+                elif x8:         # 8-bit block (always finite): genotype codes or split planes, chosen on the device
+                    _lib.check(L.pg_rotate_auto_i8_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, int(X.dtype == np.uint8), ldX,
+                                                       w.Xr.ptr, ldx, w.work.ptr, None), "pg_rotate_auto_i8_dev")
+                elif eigen and force_fp32:   # PYGEMMA_ROTATE=fp32: the reference-arithmetic kernel for every block (tests, A/B)
+                    _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, dXc.ptr, ldX, w.Xr.ptr, ldx), "pg_rotate_dev")
+                elif eigen:      # float32 block: path (genotype fp16x2 / split planes / fp32 MFMA) chosen on the device, no host wait
+                    _lib.check(L.pg_rotate_auto_dev(ctx.handle, n, pb, dU.ptr, n, dprep.ptr, dXc.ptr, ldX, w.Xr.ptr, ldx,
+                                                    w.work.ptr, None), "pg_rotate_auto_dev")
+                elif not snp_major:
+                    _lib.check(L.pg_transpose_dev(ctx.handle, n, pb, dXc.ptr, ldX, w.Xr.ptr, ldx), "pg_transpose_dev")
+                # ---- the mode's kernels, and the result rows back
+                job.mode.launch(ctx, dev, pb, w.Xr.ptr, w.res.ptr)
+                _lib.check(L.pg_memcpy_d2h_async(ctx.handle, w.out, w.res.ptr, pb * nout), "pg_memcpy_d2h_async")
+                ctx.sync()
+                return t_dma, prefetched     # (a prefetched buffer is freed with the prefetcher: hipFree would drain the device here)
 
             def worker():
                 try:
@@ -308,135 +444,36 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
                                  L.pg_geno_work_bytes(n, pb_max) if eigen else 0]
                         offs = np.concatenate([[0], np.cumsum([(int(z) + 255) // 256 * 256 for z in sizes])])
                         arena = ctx.alloc(int(offs[-1]))
-                        dX, dT, dXr, dres, dwork = (_View(arena.ptr + int(o)) if z else None for o, z in zip(offs[:-1], sizes))
-                        dXf = None       # float32 image of an 8-bit block, only if one does not qualify for the genotype path
-                        stg = _Staging(ctx, L, 0 if direct else raw_bytes, pb_max * nout)
-                        hres = (C.c_char * (pb_max * nout)).from_address(stg.out)
-                        if npheno:
-                            _lib.check(L.pg_assoc_pheno_warm(ctx.handle, n, c, npheno, pb_max), "pg_assoc_pheno_warm")
-                        elif lam0 is None:
-                            _lib.check(L.pg_assoc_warm(ctx.handle, n, c), "pg_assoc_warm")      # the first batch's kernels then queue without a host stall
+                        w = SimpleNamespace(**{k: _View(arena.ptr + int(o)) if z else None
+                                               for k, o, z in zip(("X", "T", "Xr", "res", "work"), offs[:-1], sizes)}, Xf=None)
+                        stg = _Pinned(ctx, pb_max * nout) if direct else _Pinned(ctx, raw_bytes, pb_max * nout)
+                        w.inp, w.out = (None, *stg.bufs) if direct else stg.bufs
+                        hres = (C.c_char * (pb_max * nout)).from_address(w.out)
+                        if job.mode.warm is not None:
+                            job.mode.warm(ctx, pb_max)
                         if stats is not None:
                             with lock:
                                 stats["worker_alloc_s"] = max(stats.get("worker_alloc_s", 0.0), time.time() - t_w)
                         while True:
                             with lock:
-                                if not todo or errs:
+                                if not todo or job.errs:
                                     return
                                 s, e = todo.pop(0)
-                            pb = e - s
                             t_in = time.time()
-                            pbuf, dXc = None, dX     # dXc: where this batch's raw block is
-                            # ---- the raw block travels to the device on this worker's stream
-                            if packed:   # SNP records [s, e) of the .bed image: contiguous bytes
-                                rec = X.data[s:e]
-                                if rec.flags.c_contiguous:
-                                    _lib.check(L.pg_stage_rows(stg.inp, rec.nbytes, rec.ctypes.data, rec.nbytes, rec.nbytes, 1, 1), "pg_stage_rows")
-                                else:
-                                    C.memmove(stg.inp, np.ascontiguousarray(rec).ctypes.data, pb * bpr)
-                                _lib.check(L.pg_memcpy_h2d_async(ctx.handle, dX.ptr, stg.inp, pb * bpr), "pg_memcpy_h2d_async")
-                            elif snp_major:    # SNPs [s, e) are pb contiguous rows of n floats
-                                src = X.ctypes.data + 4 * n * s
-                                dst, dpitch = (dT.ptr, 4 * n) if eigen else (dXr.ptr, 4 * ldx)       # eigen=False: already the layout the scan reads
-                                if direct:
-                                    _lib.check(L.pg_memcpy2d_h2d_async(ctx.handle, dst, dpitch, src, 4 * n, 4 * n, pb), "pg_memcpy2d_h2d_async")
-                                else:
-                                    _lib.check(L.pg_stage_rows(stg.inp, 4 * n, src, 4 * n, 4 * n, pb, _STAGE_THREADS), "pg_stage_rows")
-                                    _lib.check(L.pg_memcpy2d_h2d_async(ctx.handle, dst, dpitch, stg.inp, 4 * n, 4 * n, pb), "pg_memcpy2d_h2d_async")
-                                if eigen:      # (pb x n) -> (n x ldX): the transposition kernel with the roles of n and p exchanged
-                                    _lib.check(L.pg_transpose_dev(ctx.handle, pb, n, dT.ptr, n, dX.ptr, ldX), "pg_transpose_dev")
-                            elif pre is not None and (pbuf := pre.take(device, s, e)) is not None:
-                                dXc = pbuf       # landed on the device while the eigensolver ran
-                            else:
-                                src = X.ctypes.data + esz * s
-                                if direct:
-                                    _lib.check(L.pg_memcpy2d_h2d_async(ctx.handle, dX.ptr, ldX * esz, src, p * esz, pb * esz, n),
-                                               "pg_memcpy2d_h2d_async")
-                                else:    # pageable X: copy threads gather the column window into pinned staging, then one dense DMA
-                                    _lib.check(L.pg_stage_rows(stg.inp, ldX * esz, src, p * esz, pb * esz, n, _STAGE_THREADS), "pg_stage_rows")
-                                    _lib.check(L.pg_memcpy_h2d_async(ctx.handle, dX.ptr, stg.inp, n * ldX * esz), "pg_memcpy_h2d_async")
-                            if _SERIAL_KERNELS:
-                                ctx.sync()       # the block has landed; the kernels wait for the token, not for the link
-                            t_dma = time.time()
-                            with gpu:
-                                t_tok = time.time()
-                                # ---- rotation: decode + impute + rotate for .bed records; otherwise the path is chosen on the device
-                                if packed:
-                                    _lib.check(L.pg_rotate_bed_dev(ctx.handle, n, pb, dprep.ptr, dX.ptr, bpr, int(X.count_A1), dXr.ptr, ldx,
-                                                                   dwork.ptr), "pg_rotate_bed_dev")
-                                elif x64:
-                                    is_geno = C.c_int(0)
-                                    _lib.check(L.pg_rotate_geno_f64_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, ldX, dXr.ptr, ldx, dwork.ptr,
-                                                                        C.byref(is_geno)), "pg_rotate_geno_f64_dev")
-                                    if not is_geno.value:
-                                        dXf = dXf or ctx.alloc(n * ldX * 4)
-                                        _lib.check(L.pg_cast_f64_f32_dev(ctx.handle, n, pb, dXc.ptr, ldX, dXf.ptr, ldX), "pg_cast_f64_f32_dev")
-                                        _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, dXf.ptr, ldX, dXr.ptr, ldx), "pg_rotate_dev")
-                                elif x8:         # 8-bit block (always finite): genotype codes or split planes, chosen on the device
-                                    _lib.check(L.pg_rotate_auto_i8_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, int(X.dtype == np.uint8), ldX,
-                                                                       dXr.ptr, ldx, dwork.ptr, None), "pg_rotate_auto_i8_dev")
-                                elif eigen and force_fp32:   # PYGEMMA_ROTATE=fp32: the reference-arithmetic kernel for every block (tests, A/B)
-                                    _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, dXc.ptr, ldX, dXr.ptr, ldx), "pg_rotate_dev")
-                                elif eigen:      # float32 block: path (genotype fp16x2 / split planes / fp32 MFMA) chosen on the device, no host wait
-                                    _lib.check(L.pg_rotate_auto_dev(ctx.handle, n, pb, dU.ptr, n, dprep.ptr, dXc.ptr, ldX, dXr.ptr, ldx,
-                                                                    dwork.ptr, None), "pg_rotate_auto_dev")
-                                elif not snp_major:
-                                    _lib.check(L.pg_transpose_dev(ctx.handle, n, pb, dXc.ptr, ldX, dXr.ptr, ldx), "pg_transpose_dev")
-                                # result block: [F | p | beta | se | tau | lambda] (+ [l_alt | l_null | D_lrt | p_lrt] f64 with lrt)
-                                r0 = dres.ptr
-                                if npheno:       # the same block per phenotype-major row: [F | p | beta | se | tau | lambda], each npheno x pb
-                                    tp = npheno * pb
-                                    _lib.check(L.pg_assoc_pheno_dev(ctx.handle, n, c, pb, npheno, dd.ptr, dW.ptr, dy.ptr, n, dXr.ptr, ldx, int(grid),
-                                                                    r0 + 16 * tp, r0 + 20 * tp, r0 + 24 * tp, r0 + 28 * tp, r0, r0 + 8 * tp, None),
-                                               "pg_assoc_pheno_dev")
-                                elif lam0 is not None:
-                                    _lib.check(L.pg_score_dev(ctx.handle, n, c, pb, dd.ptr, dW.ptr, dy.ptr, float(lam0), dXr.ptr, ldx,
-                                                              r0 + 16 * pb, r0 + 20 * pb, r0 + 24 * pb, r0 + 28 * pb, r0, r0 + 8 * pb), "pg_score_dev")
-                                elif lrt:
-                                    _lib.check(L.pg_assoc_lrt_dev(ctx.handle, n, c, pb, dd.ptr, dW.ptr, dy.ptr, dXr.ptr, ldx, int(grid),
-                                                                  r0 + 16 * pb, r0 + 20 * pb, r0 + 24 * pb, r0 + 28 * pb, r0, r0 + 8 * pb,
-                                                                  r0 + 32 * pb, r0 + 40 * pb, r0 + 48 * pb, r0 + 56 * pb), "pg_assoc_lrt_dev")
-                                else:
-                                    _lib.check(L.pg_assoc_dev(ctx.handle, n, c, pb, dd.ptr, dW.ptr, dy.ptr, dXr.ptr, ldx, int(grid),
-                                                              r0 + 16 * pb, r0 + 20 * pb, r0 + 24 * pb, r0 + 28 * pb, r0, r0 + 8 * pb, None),
-                                               "pg_assoc_dev")
-                                _lib.check(L.pg_memcpy_d2h_async(ctx.handle, stg.out, r0, pb * nout), "pg_memcpy_d2h_async")
-                                ctx.sync()
-                                t_ker = time.time()
-                            if pbuf is not None and stats is not None:      # (the buffer is freed with the prefetcher: hipFree would drain the device here)
-                                with lock:
-                                    stats["prefetched_batches"] = stats.get("prefetched_batches", 0) + 1
-                            hb = np.frombuffer(hres, np.uint8, pb * nout)
-                            if npheno:
-                                tp = npheno * pb
-                                FP = hb[:16 * tp].view(np.float64).reshape(2, npheno, pb)
-                                res = hb[16 * tp:32 * tp].view(np.float32).reshape(4, npheno, pb)
-                                out["beta"][:, s:e], out["se_beta"][:, s:e], out["tau"][:, s:e] = res[0], res[1], res[2]
-                                out["lambda"][:, s:e] = res[3].astype(np.float64)
-                                out["F_wald"][:, s:e], out["p_wald"][:, s:e] = FP[0], FP[1]
-                            else:
-                                FP = hb[:16 * pb].view(np.float64).reshape(2, pb)
-                                res = hb[16 * pb:32 * pb].view(np.float32).reshape(4, pb)
-                                out["beta"][s:e], out["se_beta"][s:e], out["tau"][s:e] = res[0], res[1], res[2]
-                                out["lambda"][s:e] = res[3].astype(np.float64)
-                                out["F_wald"][s:e], out["p_wald"][s:e] = FP[0], FP[1]
-                            if lrt:
-                                LR = hb[32 * pb:64 * pb].view(np.float64).reshape(4, pb)
-                                for k, col in enumerate(_LRT_COLS):
-                                    out[col][s:e] = LR[k]
+                            t_dma, prefetched = batch(ctx, w, s, e)
+                            t_ker = time.time()
+                            job.mode.decode(hres, job.out, s, e)
                             if stats is not None:
                                 with lock:
+                                    if prefetched:
+                                        stats["prefetched_batches"] = stats.get("prefetched_batches", 0) + 1
                                     stats["batches"] += 1
-                                    stats["bytes_in"] += pb * bpr if packed else n * pb * esz
+                                    stats["bytes_in"] += (e - s) * bpr if packed else n * (e - s) * esz
                                     stats["batch_s"] += time.time() - t_in
-                                    stats["dma_s"] = stats.get("dma_s", 0.0) + (t_dma - t_in)       # copy-in (waited for only when the kernels are serialised)
-                                    stats["token_s"] = stats.get("token_s", 0.0) + (t_tok - t_dma)  # waiting for the other worker's kernels
-                                    stats["kernel_s"] = stats.get("kernel_s", 0.0) + (t_ker - t_tok)
-                            if ckpt:
-                                tmp = _part_path(ckpt, s, e) + ".tmp.npz"
-                                np.savez(tmp, fingerprint=np.int64(_block_fingerprint(X, s, e)),
-                                         **{col: out[col][s:e] for col in _COLS + (_LRT_COLS if lrt else ())})
-                                os.replace(tmp, _part_path(ckpt, s, e))
+                                    stats["dma_s"] = stats.get("dma_s", 0.0) + (t_dma - t_in)       # copy-in: staging + DMA issue
+                                    stats["kernel_s"] = stats.get("kernel_s", 0.0) + (t_ker - t_dma)
+                            if job.ckpt:
+                                _save_part(job, s, e)
                             _log(verbose, f"GPU {device}: SNPs [{s},{e}) done")
                     finally:
                         t_td = time.time()
@@ -448,7 +485,7 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
                             with lock:
                                 stats["worker_teardown_s"] = max(stats.get("worker_teardown_s", 0.0), time.time() - t_td)
                 except Exception as ex:  # surfaced by the caller; never swallowed
-                    errs.append(ex)
+                    job.errs.append(ex)
 
             workers = [threading.Thread(target=worker) for _ in range(min(_WORKERS, len(todo)))]
             for th in workers:
@@ -462,7 +499,7 @@ def _run_block(device, a, b, n, c, d, Wr, yr, X, dU, comm, grid, eigen, lrt, out
             if stats is not None:
                 stats["block_teardown_s"] = max(stats.get("block_teardown_s", 0.0), time.time() - t_td)
     except Exception as ex:  # surfaced by the caller; never swallowed
-        errs.append(ex)
+        job.errs.append(ex)
 
 
 class _Comm:
@@ -568,12 +605,9 @@ def _kinship_stream(G, standardize, device, snp_batch):
         dacc = ctx.alloc(L.pg_kinship_acc_bytes(n, pb))
         dK = ctx.alloc(4 * n * n)
         slots = [ctx.alloc(pb * row_bytes) for _ in range(2)]
-        staging, events = [], []
+        stg = _Pinned(up, *[pb * row_bytes] * (0 if direct else 2))
+        events = []
         try:
-            for _ in range(0 if direct else 2):
-                h = C.c_void_p()
-                _lib.check(L.pg_host_alloc(up.handle, pb * row_bytes, C.byref(h)), "pg_host_alloc")
-                staging.append(h.value)
             for c_ in (up, up, ctx, ctx):
                 ev = C.c_void_p()
                 _lib.check(L.pg_event_create(c_.handle, C.byref(ev)), "pg_event_create")
@@ -581,37 +615,16 @@ def _kinship_stream(G, standardize, device, snp_batch):
             ev_up, ev_done = events[:2], events[2:]
             _lib.check(L.pg_memset(ctx.handle, dacc.ptr, 0, 8 * n * n), "pg_memset")
             batches = [(s, min(s + pb, p)) for s in range(0, p, pb)]
-            base = src_arr.ctypes.data
 
             def upload(b):
                 s, e = batches[b]
-                k, w = b % 2, e - s
+                k = b % 2
                 if b >= 2:
                     _lib.check(L.pg_stream_wait_event(up.handle, ev_done[k]), "pg_stream_wait_event")   # batch b-2 is done with the slot
-                if packed and not src_arr.flags.c_contiguous:
-                    rec = np.ascontiguousarray(src_arr[s:e])
-                    if b >= 2:
-                        _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")
-                    C.memmove(staging[k], rec.ctypes.data, rec.nbytes)
-                    _lib.check(L.pg_memcpy_h2d_async(up.handle, slots[k].ptr, staging[k], rec.nbytes), "pg_memcpy_h2d_async")
-                elif snp_major:        # SNP records [s, e): contiguous bytes
-                    src = base + s * row_bytes
-                    if direct:
-                        _lib.check(L.pg_memcpy_h2d_async(up.handle, slots[k].ptr, src, w * row_bytes), "pg_memcpy_h2d_async")
-                    else:
-                        if b >= 2:
-                            _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")    # the DMA of batch b-2 has left the staging
-                        _lib.check(L.pg_stage_rows(staging[k], row_bytes, src, row_bytes, row_bytes, w, _STAGE_THREADS), "pg_stage_rows")
-                        _lib.check(L.pg_memcpy_h2d_async(up.handle, slots[k].ptr, staging[k], w * row_bytes), "pg_memcpy_h2d_async")
-                else:                  # sample-major: the column window [s, e) of every row, packed to row stride w
-                    src = base + s * esz
-                    if direct:
-                        _lib.check(L.pg_memcpy2d_h2d_async(up.handle, slots[k].ptr, w * esz, src, p * esz, w * esz, n), "pg_memcpy2d_h2d_async")
-                    else:
-                        if b >= 2:
-                            _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")
-                        _lib.check(L.pg_stage_rows(staging[k], w * esz, src, p * esz, w * esz, n, _STAGE_THREADS), "pg_stage_rows")
-                        _lib.check(L.pg_memcpy_h2d_async(up.handle, slots[k].ptr, staging[k], n * w * esz), "pg_memcpy_h2d_async")
+                    if not direct:
+                        _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")    # the DMA of batch b-2 has left the staging
+                # SNP-major: the records / columns [s, e) back to back; sample-major: the column window of every row at row stride e - s
+                _put_window(up, G, s, e, slots[k].ptr, None if snp_major else (e - s) * esz, None if direct else stg.bufs[k])
                 _lib.check(L.pg_event_record(up.handle, ev_up[k]), "pg_event_record")
 
             upload(0)
@@ -635,8 +648,7 @@ def _kinship_stream(G, standardize, device, snp_batch):
             ctx.sync()
             for ev in events:
                 L.pg_event_destroy(up.handle, ev)
-            for h in staging:
-                L.pg_host_free(up.handle, h)
+            stg.close()
 
 
 def _zkzt(L, Z, K):
@@ -682,9 +694,9 @@ def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=Fa
     if de:
         # calculate_de is broken upstream (unpacks 4 of SampleIter's 5-tuple, lmm/lmm.py:499 vs :434)
         raise NotImplementedError("de=True is broken in the reference (lmm/lmm.py:499) and is not provided")
-    out = _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint, lrt, eigenpairs, stats, 0)
-    cols = list(_COLS) + (list(_LRT_COLS) if lrt else [])
-    results_df = pd.DataFrame(out, columns=cols)                                                     # lmm.py:403
+    out = _scan(Y, X, W, K, Z=Z, verbose=verbose, disable_checks=disable_checks, grid=grid, eigen=eigen, nproc=nproc,
+                checkpoint=checkpoint, lrt=lrt, eigenpairs=eigenpairs, stats=stats)
+    results_df = pd.DataFrame(out, columns=list(out))                                                # lmm.py:403
     if snps is not None:
         results_df["SNPs"] = snps                                                                    # lmm.py:408-409
     return results_df
@@ -721,7 +733,8 @@ def pygemma_multi(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True,
     Y32 = np.empty((n, len(cols)), np.float32)
     for k, col in enumerate(cols):
         Y32[:, k] = col.astype(np.float32)                   # lmm.py:115-116, per column
-    out = _scan(Y32, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, None, False, eigenpairs, stats, len(cols))
+    out = _scan(Y32, X, W, K, Z=Z, verbose=verbose, disable_checks=disable_checks, grid=grid, eigen=eigen, nproc=nproc,
+                eigenpairs=eigenpairs, stats=stats, npheno=len(cols))
     res = {}
     for k, lab in enumerate(labels):
         df = pd.DataFrame({col: out[col][k] for col in _COLS}, columns=list(_COLS))
@@ -744,7 +757,8 @@ def pygemma_score(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True,
     A SNP that is constant or lies in span(W) (P_xx <= 1e-10 x'Hx), or holds a NaN/inf, gets NaN in every column but lambda; a
     rank-deficient W gives NaN rows throughout.  No grid (the null search is Brent's), lrt or checkpoint.  `stats` receives
     lmm.pygemma's counters plus `lambda_null`."""
-    out = _scan(Y, X, W, K, Z, verbose, disable_checks, False, eigen, nproc, None, False, eigenpairs, stats, 0, score=True)
+    out = _scan(Y, X, W, K, Z=Z, verbose=verbose, disable_checks=disable_checks, eigen=eigen, nproc=nproc, eigenpairs=eigenpairs,
+                stats=stats, score=True)
     results_df = pd.DataFrame({"beta": out["beta"], "se_beta": out["se_beta"], "tau": out["tau"], "lambda": out["lambda"],
                                "F_score": out["F_wald"], "p_score": out["p_wald"]})
     if snps is not None:
@@ -761,11 +775,9 @@ def _null_lambda(L, n, c, d, Wr, yr):
         return np.float32(dl.download((1,), np.float32)[0])
 
 
-def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint, lrt, eigenpairs, stats, npheno, score=False):
-    """The pipeline under pygemma (npheno = 0: Y is one phenotype), pygemma_multi (Y: float32 (n, npheno)) and pygemma_score
-    (score = True: F_wald / p_wald hold F_score / p_score).  Returns the result columns: arrays of p values, or npheno x p with
-    npheno > 0."""
-    L = _lib.load()
+def _inputs(L, Y, X, W, K, Z, eigen, eigenpairs, score):
+    """Checks and casts of the inputs (lmm.py:113-128), all before any device is touched but _zkzt's: Y, X, W, K as the scan takes
+    them."""
     packed = isinstance(X, PackedBed)                         # extension (SURVEY 8f N4): a PLINK .bed image instead of the float matrix
     if packed and not eigen:
         raise ValueError("a PackedBed holds raw genotypes: it cannot be used with eigen=False (pre-rotated inputs)")
@@ -775,7 +787,6 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
     K = np.asarray(K) if K is not None else None
     if not packed:
         X = np.asarray(X)
-    nproc = min(int(nproc), X.shape[1])                      # lmm.py:113
     if Y.dtype != np.float32:
         Y = Y.astype(np.float32).reshape(-1, 1)              # lmm.py:115-116
     if W.dtype != np.float32:
@@ -796,9 +807,7 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
     snp_major = (not packed) and X.ndim == 2 and X.dtype == np.float32 and X.flags.f_contiguous and not X.flags.c_contiguous
     if not packed and not X.flags.c_contiguous and not snp_major:
         X = np.ascontiguousarray(X)
-    n, p = X.shape
-    c = W.shape[1]
-    ty = npheno or 1                                         # phenotype columns of Y that are used
+    n, c = X.shape[0], W.shape[1]
     if Y.shape[0] != n or W.shape[0] != n:
         raise ValueError(f"shape mismatch: Y {Y.shape}, X {X.shape}, W {W.shape}")
     if score:
@@ -806,6 +815,95 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
             raise ValueError(f"the score test takes 1 to 30 covariates, got W {W.shape}")
         if n - c - 1 <= 0:
             raise ValueError(f"the score test needs n - c - 1 > 0 (n = {n}, c = {c})")
+    return Y, X, W, K
+
+
+def _eigenbasis(L, ectx, n, Y, W, K, eigenpairs, ty, verbose, t0):
+    """U on GPU 0 (ectx's device) — from the host `eigenpairs`, or pg_syevd_dev of K — and [Y | W] rotated by it: returns the
+    eigenvalues, U and the rotated first `ty` columns of Y and W."""
+    if eigenpairs is not None:
+        ev, Uh = eigenpairs
+        Uh = np.asarray(Uh)
+        if Uh.shape != (n, n):
+            raise ValueError(f"eigenpairs: U must be ({n},{n}), got {Uh.shape}")
+        if Uh.dtype != np.float32 or not Uh.flags.c_contiguous:
+            Uh = np.ascontiguousarray(Uh, np.float32)                       # lmm.py:154
+        eigenVals = np.maximum(0.0, np.asarray(ev)).astype(np.float32).reshape(-1)   # lmm.py:157-160
+        if eigenVals.shape[0] != n:
+            raise ValueError(f"eigenpairs: {n} eigenvalues expected, got {eigenVals.shape}")
+        dU0 = ectx.alloc(n * n * 4)
+        # U's n rows of n floats are the SNP-major rows of Uh.T
+        if _lib.is_pinned(Uh):     # one DMA straight out of the caller's pinned array
+            _put_window(ectx, Uh.T, 0, n, dU0.ptr)
+            ectx.sync()
+        else:                      # pageable: row panels through two pinned buffers, copy threads ahead of the DMA
+            rows = max(1, min(n, (256 << 20) // (n * 4)))
+            halves = _Pinned(ectx, rows * n * 4, rows * n * 4)
+            try:
+                evs = [C.c_void_p(), C.c_void_p()]
+                for e_ in evs:
+                    _lib.check(L.pg_event_create(ectx.handle, C.byref(e_)), "pg_event_create")
+                for j, r0 in enumerate(range(0, n, rows)):
+                    k = j % 2
+                    if j >= 2:         # the DMA of panel j - 2 has left this buffer
+                        _lib.check(L.pg_event_sync(ectx.handle, evs[k]), "pg_event_sync")
+                    _put_window(ectx, Uh.T, r0, min(n, r0 + rows), dU0.ptr + r0 * n * 4, staging=halves.bufs[k])
+                    _lib.check(L.pg_event_record(ectx.handle, evs[k]), "pg_event_record")
+                ectx.sync()
+                for e_ in evs:
+                    L.pg_event_destroy(ectx.handle, e_)
+            finally:
+                halves.close()
+        _log(verbose, f"Eigenvectors uploaded ({n * n * 4 / 1e9:.2f} GB) - {time.time() - t0:.3f} s")
+    else:
+        if K.shape != (n, n):
+            raise ValueError(f"K must be ({n},{n}) when eigen=True, got {K.shape}")
+        if K.dtype == np.float64:
+            dK64 = ectx.to_device(np.ascontiguousarray(K))
+            dK = ectx.alloc(n * n * 4)
+            _lib.check(L.pg_cast_f64_f32_dev(ectx.handle, n, n, dK64.ptr, n, dK.ptr, n), "pg_cast_f64_f32_dev")   # lmm.py:127-128
+            ectx.sync()
+            dK64.free()
+        else:
+            dK = ectx.to_device(K)
+        dev, dU0 = ectx.alloc(n * 4), ectx.alloc(n * n * 4)
+        _lib.check(L.pg_syevd_dev(ectx.handle, n, dK.ptr, dev.ptr, dU0.ptr, None, None), "pg_syevd_dev")
+        dK.free()
+        eigenVals = dev.download((n,), np.float32)       # ascending, clamped >= 0, float32 (lmm.py:152-160)
+        _log(verbose, f"Eigendecomposition computed - {time.time() - t0:.3f} s")
+    assert (eigenVals >= 0).all()                        # lmm.py:162
+    t1 = time.time()
+    # [Y | W] in one rotation: an output column's bits do not depend on the columns beside it (rotate.hip)
+    YW = _rotate_small(ectx, L, n, dU0, np.concatenate([Y.reshape(n, -1)[:, :ty], W], axis=1))
+    _log(verbose, f"Left multiplied Y, W by U.T - {time.time() - t1:.3f} s")
+    return eigenVals, dU0, YW[:, :ty], np.ascontiguousarray(YW[:, ty:])
+
+
+def _check_manifest(checkpoint, key):
+    """The checkpoint directory's manifest.json: written on the first run, and a rerun with another `key` is refused."""
+    os.makedirs(checkpoint, exist_ok=True)
+    mf = os.path.join(checkpoint, "manifest.json")
+    if os.path.exists(mf):
+        with open(mf) as f:
+            if json.load(f) != key:
+                raise ValueError(f"checkpoint directory {checkpoint} belongs to a different run (manifest mismatch)")
+    else:
+        with open(mf, "w") as f:
+            json.dump(key, f)
+
+
+def _scan(Y, X, W, K, *, Z=None, verbose=0, disable_checks=True, grid=False, eigen=True, nproc=1, checkpoint=None, lrt=False,
+          eigenpairs=None, stats=None, npheno=0, score=False):
+    """The pipeline under pygemma (npheno = 0: Y is one phenotype), pygemma_multi (Y: float32 (n, npheno)) and pygemma_score
+    (score = True: F_wald / p_wald hold F_score / p_score).  Returns the result columns: arrays of p values, or npheno x p with
+    npheno > 0."""
+    L = _lib.load()
+    Y, X, W, K = _inputs(L, Y, X, W, K, Z, eigen, eigenpairs, score)
+    packed = isinstance(X, PackedBed)
+    nproc = min(int(nproc), X.shape[1])                      # lmm.py:113
+    n, p = X.shape
+    c = W.shape[1]
+    ty = npheno or 1                                         # phenotype columns of Y that are used
     ngpu = _lib.device_count()
     if ngpu < 1:
         raise _lib.PgError("no MI355X visible: pygemma_amd has no CPU path")
@@ -814,12 +912,12 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
 
     t0 = time.time()
     ectx = dU0 = None  # the eigensolver's context on GPU 0 and U resident there (reused by GPU 0's SNP loop)
-    xpin = pre = None
-    pin_thread, pin_box = None, {}    # page-locking of a pageable X beside the eigensolver
-    comms = None
+    xpin = pre = pin_thread = comms = None
+    pin_box = {}       # page-locking of a pageable X beside the eigensolver
+    errs = []
     # ONE try/finally owns every resource made from here on (prefetch contexts and threads, the page-lock of X, the communicators,
-    # the eigensolver's context): whatever raises in between — a bad K, os.makedirs, the manifest, a worker — they are released
-    # (every close() below is idempotent, so the earlier explicit ones stay harmless)
+    # the eigensolver's context): whatever raises in between — a bad K or U, NaNs, the manifest, a GPU's block — releases them all
+    # in the order of the finally clause
     try:
         if eigen and eigenpairs is None and not packed and not checkpoint and X.flags.c_contiguous and _PREFETCH_MAX > 0:
             # the eigensolver leaves PCIe idle for ~0.6 s at n = 10 000 (52 s at 50 000): X starts moving now
@@ -841,75 +939,7 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
             pin_thread.start()
         if eigen:
             ectx = _lib.Context(0)
-            try:
-                if eigenpairs is not None:
-                    ev, Uh = eigenpairs
-                    Uh = np.asarray(Uh)
-                    if Uh.shape != (n, n):
-                        raise ValueError(f"eigenpairs: U must be ({n},{n}), got {Uh.shape}")
-                    if Uh.dtype != np.float32 or not Uh.flags.c_contiguous:
-                        Uh = np.ascontiguousarray(Uh, np.float32)                       # lmm.py:154
-                    eigenVals = np.maximum(0.0, np.asarray(ev)).astype(np.float32).reshape(-1)   # lmm.py:157-160
-                    if eigenVals.shape[0] != n:
-                        raise ValueError(f"eigenpairs: {n} eigenvalues expected, got {eigenVals.shape}")
-                    dU0 = ectx.alloc(n * n * 4)
-                    if _lib.is_pinned(Uh):     # one DMA straight out of the caller's pinned array
-                        _lib.check(L.pg_memcpy_h2d_async(ectx.handle, dU0.ptr, Uh.ctypes.data, Uh.nbytes), "pg_memcpy_h2d_async")
-                        ectx.sync()
-                    else:                      # pageable: row panels through a pinned double buffer, copy threads ahead of the DMA
-                        rows = max(1, min(n, (256 << 20) // (n * 4)))
-                        stg = _Staging(ectx, L, rows * n * 4, rows * n * 4)      # .inp / .out used as the two halves
-                        try:
-                            halves, k = (stg.inp, stg.out), 0
-                            evs = [C.c_void_p(), C.c_void_p()]
-                            for e_ in evs:
-                                _lib.check(L.pg_event_create(ectx.handle, C.byref(e_)), "pg_event_create")
-                            used = [False, False]
-                            for r0 in range(0, n, rows):
-                                r1 = min(n, r0 + rows)
-                                if used[k]:
-                                    _lib.check(L.pg_event_sync(ectx.handle, evs[k]), "pg_event_sync")
-                                _lib.check(L.pg_stage_rows(halves[k], n * 4, Uh.ctypes.data + r0 * n * 4, n * 4, n * 4, r1 - r0, _STAGE_THREADS),
-                                           "pg_stage_rows")
-                                _lib.check(L.pg_memcpy_h2d_async(ectx.handle, dU0.ptr + r0 * n * 4, halves[k], (r1 - r0) * n * 4), "pg_memcpy_h2d_async")
-                                _lib.check(L.pg_event_record(ectx.handle, evs[k]), "pg_event_record")
-                                used[k] = True
-                                k ^= 1
-                            ectx.sync()
-                            for e_ in evs:
-                                L.pg_event_destroy(ectx.handle, e_)
-                        finally:
-                            stg.close()
-                    _log(verbose, f"Eigenvectors uploaded ({n * n * 4 / 1e9:.2f} GB) - {time.time() - t0:.3f} s")
-                else:
-                    if K.shape != (n, n):
-                        raise ValueError(f"K must be ({n},{n}) when eigen=True, got {K.shape}")
-                    if k64:
-                        dK64 = ectx.to_device(np.ascontiguousarray(K))
-                        dK = ectx.alloc(n * n * 4)
-                        _lib.check(L.pg_cast_f64_f32_dev(ectx.handle, n, n, dK64.ptr, n, dK.ptr, n), "pg_cast_f64_f32_dev")   # lmm.py:127-128
-                        ectx.sync()
-                        dK64.free()
-                    else:
-                        dK = ectx.to_device(K)
-                    dev, dU0 = ectx.alloc(n * 4), ectx.alloc(n * n * 4)
-                    _lib.check(L.pg_syevd_dev(ectx.handle, n, dK.ptr, dev.ptr, dU0.ptr, None, None), "pg_syevd_dev")
-                    dK.free()
-                    eigenVals = dev.download((n,), np.float32)       # ascending, clamped >= 0, float32 (lmm.py:152-160)
-                    _log(verbose, f"Eigendecomposition computed - {time.time() - t0:.3f} s")
-                assert (eigenVals >= 0).all()                    # lmm.py:162
-                t1 = time.time()
-                # [Y | W] in one rotation: an output column's bits do not depend on the columns beside it (rotate.hip)
-                YW = _rotate_small(ectx, L, n, dU0, np.concatenate([Y.reshape(n, -1)[:, :ty], W], axis=1))
-                Yr, Wr = YW[:, :ty], np.ascontiguousarray(YW[:, ty:])
-                _log(verbose, f"Left multiplied Y, W by U.T - {time.time() - t1:.3f} s")
-            except BaseException:
-                if pre is not None:
-                    pre.close()
-                if xpin is not None:
-                    xpin.close()
-                ectx.close()
-                raise
+            eigenVals, dU0, Yr, Wr = _eigenbasis(L, ectx, n, Y, W, K, eigenpairs, ty, verbose, t0)
         else:
             eigenVals = np.maximum(0.0, K).astype(np.float32).reshape(-1)   # lmm.py:166-167
             if eigenVals.shape[0] != n:
@@ -920,12 +950,6 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
             # lmm.py:253-256 (the reference tests the rotated arrays; a NaN anywhere in a raw column makes that
             # whole rotated column NaN, so testing the inputs raises in exactly the same cases)
             if (not packed and X.dtype.kind == 'f' and np.isnan(X).any()) or np.isnan(Yr).any() or np.isnan(Wr).any():
-                if pre is not None:
-                    pre.close()
-                if xpin is not None:
-                    xpin.close()
-                if ectx is not None:
-                    ectx.close()
                 raise ValueError("NaNs present in data")
 
         _log(verbose, f"Running {p} SNPs with {n} individuals on {ndev} GPU(s)...")
@@ -935,7 +959,6 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
         if lrt:
             for col in _LRT_COLS:
                 out[col] = np.empty(p, np.float64)
-        errs, threads = [], []
         if stats is not None:
             stats.update({"batches": 0, "bytes_in": 0, "batch_s": 0.0, "gpus": ndev})
             if npheno:
@@ -948,89 +971,59 @@ def _scan(Y, X, W, K, Z, verbose, disable_checks, grid, eigen, nproc, checkpoint
             if stats is not None:
                 stats["lambda_null"] = float(lam0)
         if checkpoint:
-            os.makedirs(checkpoint, exist_ok=True)
             # identity of the run: shapes, options, batch geometry and the SNP-independent inputs themselves (rotated y, W and the
             # eigenvalues, byte for byte); the genotypes are fingerprinted per part (_block_fingerprint)
-            key = {"n": int(n), "p": int(p), "c": int(c), "grid": bool(grid), "eigen": bool(eigen), "ndev": int(ndev), "lrt": bool(lrt),
-                   "batch_snps": int(_BATCH_SNPS), "batch_bytes": int(_BATCH_BYTES), "batch_min": int(_BATCH_MIN), "batch_count": int(_BATCH_COUNT),
-                   "y_crc": _crc(yr1), "w_crc": _crc(Wr), "d_crc": _crc(eigenVals)}
-            mf = os.path.join(checkpoint, "manifest.json")
-            if os.path.exists(mf):
-                with open(mf) as f:
-                    if json.load(f) != key:
-                        if ectx is not None:
-                            ectx.close()
-                        raise ValueError(f"checkpoint directory {checkpoint} belongs to a different run (manifest mismatch)")
-            else:
-                with open(mf, "w") as f:
-                    json.dump(key, f)
+            _check_manifest(checkpoint, {
+                "n": int(n), "p": int(p), "c": int(c), "grid": bool(grid), "eigen": bool(eigen), "ndev": int(ndev), "lrt": bool(lrt),
+                "batch_snps": int(_BATCH_SNPS), "batch_bytes": int(_BATCH_BYTES), "batch_min": int(_BATCH_MIN), "batch_count": int(_BATCH_COUNT),
+                "y_crc": _crc(yr1), "w_crc": _crc(Wr), "d_crc": _crc(eigenVals)})
         t2 = time.time()
-        comms = None
-        try:
-            if pre is not None:
-                pre.join()
-                if stats is not None:
-                    stats["prefetched_bytes"] = int(pre.bytes)
-            if pin_thread is not None:
-                pin_thread.join()
-                pin_thread = None
-                xpin = pin_box.pop("h", None)
-                if "err" in pin_box:
-                    _log(verbose, f"X could not be page-locked in place ({pin_box['err']}); staging through pinned buffers")
-            elif not packed and not _lib.is_pinned(X):
-                # page-lock the caller's X in place for the duration of the scan (hipHostRegister: 2 ms/GB for a range the kernel has pinned
-                # before, ~60 ms/GB the first time: tools/probe_pageable.py) so that every batch is one 2-D DMA straight out of it; if the
-                # range cannot be registered (e.g. a read-only file mapping) the workers fall back to copy threads + a pinned staging buffer
-                try:
-                    xpin = _lib.pin(X)
-                except _lib.PgError as ex:
-                    _log(verbose, f"X could not be page-locked in place ({ex}); staging through pinned buffers")
+        if pre is not None:
+            pre.join()
             if stats is not None:
-                stats["pinned_input"] = bool((not packed) and _lib.is_pinned(X))
-                stats["registered_in_place"] = xpin is not None
-            dUs = [dU0] + [None] * (ndev - 1)
-            if ndev > 1 and eigen:
-                comms = _make_comms(L, ndev)      # RCCL communicator over the GPUs of this process: U goes GPU 0 -> all over xGMI
-                for g in range(1, ndev):          # receive buffers made here: an allocation failure surfaces before any thread waits in the collective
-                    dUs[g] = comms[g].ctx.alloc(n * n * 4)
-            for dev_id, (a, b) in enumerate(blocks):
-                th = threading.Thread(target=_run_block, args=(dev_id, a, b, n, c, eigenVals, Wr, yr1, X,
-                                                               dUs[dev_id], comms[dev_id] if comms else None,
-                                                               grid, eigen, lrt, out, errs, verbose, checkpoint, stats, pre, npheno, lam0))
-                th.start()
-                threads.append(th)
-            for th in threads:
-                th.join()
-            if stats is not None:
-                stats["blocks_s"] = time.time() - t2          # page-locking + every GPU's block; what follows is teardown (frees)
-        finally:
-            if pre is not None:
-                pre.close()
-            if xpin is not None:
-                xpin.close()
-            if comms:
-                for cm in comms:
-                    if cm.handle:
-                        L.pg_comm_destroy(cm.handle)
-                        cm.handle = None
-                    cm.ctx.close()
-            if ectx is not None:
-                ectx.close()
+                stats["prefetched_bytes"] = int(pre.bytes)
+        if pin_thread is not None:
+            pin_thread.join()
+            xpin = pin_box.pop("h", None)
+            if "err" in pin_box:
+                _log(verbose, f"X could not be page-locked in place ({pin_box['err']}); staging through pinned buffers")
+        elif not packed and not _lib.is_pinned(X):
+            # page-lock the caller's X in place for the duration of the scan (hipHostRegister: 2 ms/GB for a range the kernel has pinned
+            # before, ~60 ms/GB the first time: tools/probe_pageable.py) so that every batch is one 2-D DMA straight out of it; if the
+            # range cannot be registered (e.g. a read-only file mapping) the workers fall back to copy threads + a pinned staging buffer
+            try:
+                xpin = _lib.pin(X)
+            except _lib.PgError as ex:
+                _log(verbose, f"X could not be page-locked in place ({ex}); staging through pinned buffers")
+        if stats is not None:
+            stats["pinned_input"] = bool((not packed) and _lib.is_pinned(X))
+            stats["registered_in_place"] = xpin is not None
+        dUs = [dU0] + [None] * (ndev - 1)
+        if ndev > 1 and eigen:
+            comms = _make_comms(L, ndev)      # RCCL communicator over the GPUs of this process: U goes GPU 0 -> all over xGMI
+            for g in range(1, ndev):          # receive buffers made here: an allocation failure surfaces before any thread waits in the collective
+                dUs[g] = comms[g].ctx.alloc(n * n * 4)
+        job = _Job(n, c, eigenVals, Wr, yr1, X, grid, eigen, _scan_mode(L, n, c, grid, lrt, npheno, lam0), checkpoint, stats, pre,
+                   verbose, out, errs)
+        threads = [threading.Thread(target=_run_block, args=(job, g, a, b, dUs[g], comms[g] if comms else None))
+                   for g, (a, b) in enumerate(blocks)]
+        for th in threads:
+            th.start()
+        for th in threads:
+            th.join()
+        if stats is not None:
+            stats["blocks_s"] = time.time() - t2          # page-locking + every GPU's block; what follows is teardown (frees)
     finally:
         if pre is not None:
-            pre.close()
-        if pin_thread is not None:        # an exception before the loop: the registration may still be under way
+            pre.close()                   # frees the prefetched batches only now: hipFree inside the loop would drain the device
+        if pin_thread is not None:        # something raised while X was being page-locked: wait for it, and undo it below
             pin_thread.join()
-            if pin_box.get("h") is not None:
-                pin_box.pop("h").close()
+            xpin = xpin or pin_box.pop("h", None)
         if xpin is not None:
             xpin.close()
-        if comms:
-            for cm in comms:
-                if cm.handle:
-                    L.pg_comm_destroy(cm.handle)
-                    cm.handle = None
-                cm.ctx.close()
+        for cm in comms or ():
+            L.pg_comm_destroy(cm.handle)
+            cm.ctx.close()
         if ectx is not None:
             ectx.close()
     if errs:

@@ -314,3 +314,47 @@ def test_config4_one_gpu_share_n10000_c10_p125000_streamed():
     for col in COLS[:5]:
         assert (bits(df[col].to_numpy()[idx]) == bits(orc[col].astype(df[col].dtype))).all(), col
     np.testing.assert_allclose(df["p_wald"].to_numpy()[idx], orc["p_wald"], rtol=1e-9)
+
+
+def test_refused_and_failing_scans_release_everything(tmp_path, monkeypatch):
+    """A scan that raises after the eigensolver's context, the prefetcher, the page-lock of X or a GPU's block has been set up
+    releases all of them: after a warm-up round, one more round of the four failures leaves the device's free memory and the
+    number of threads where they were.  X is 256 MB, so a pageable X is page-locked on a thread beside the eigensolver."""
+    import threading
+    from pygemma_amd import _lib, lmm
+    n, p, c = 4096, 16384, 3
+    rng = np.random.default_rng(77)
+    X = rng.integers(0, 3, size=(n, p)).astype(np.float32)
+    X2 = X.copy()
+    X2[0] += 1                                               # other genotypes: every checkpoint part's fingerprint differs
+    Xp = lmm.pinned_empty((n, p), np.float32)
+    Xp[:] = X
+    G = rng.standard_normal((n, 256), dtype=np.float32)
+    K = G @ G.T / 256
+    W = np.concatenate([np.ones((n, 1)), rng.standard_normal((n, c - 1))], axis=1).astype(np.float32)
+    Y = rng.standard_normal((n, 1)).astype(np.float32)
+    Ynan = Y.copy()
+    Ynan[5] = np.nan
+    ckpt = str(tmp_path / "ckpt")
+    lmm.pygemma(Y, X, W, K, checkpoint=ckpt)                 # the run whose manifest and parts the failures below meet
+
+    def failures():
+        monkeypatch.setattr(lmm, "_PREFETCH_MAX", 96 << 30)
+        with pytest.raises(ValueError, match="NaNs present"):           # eigensolver context, U and the prefetcher are live
+            lmm.pygemma(Ynan, Xp, W, K, disable_checks=False)
+        monkeypatch.setattr(lmm, "_PREFETCH_MAX", 0)
+        with pytest.raises(ValueError, match="manifest mismatch"):
+            lmm.pygemma(Y + 1, X, W, K, checkpoint=ckpt)
+        with pytest.raises(ValueError, match="different genotypes"):    # raised in GPU 0's block thread, surfaced through errs
+            lmm.pygemma(Y, X2, W, K, checkpoint=ckpt)
+        with pytest.raises(ValueError, match="U must be"):
+            lmm.pygemma(Y, X, W, None, eigenpairs=(np.ones(n), np.eye(n - 1, dtype=np.float32)))
+        assert not _lib.is_pinned(X) and not _lib.is_pinned(X2)
+
+    with _lib.Context(0) as ctx:
+        failures()                                           # warm-up: code objects, pools, first-use allocations
+        free0, threads0 = ctx.mem_info()[0], threading.active_count()
+        failures()
+        free1, threads1 = ctx.mem_info()[0], threading.active_count()
+    assert abs(free1 - free0) <= (32 << 20), f"free device memory {free0} -> {free1}"    # U alone is 64 MB
+    assert threads1 == threads0
