@@ -179,6 +179,22 @@ int pg_score_null_dev(pg_ctx *ctx, int64_t n, int c, const float *d, const float
 int pg_score_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, const float *Wr, const float *yr, float lambda0,
                  const float *Xr, int64_t ldx, float *beta, float *se, float *tau, float *lambda, double *F, double *pval);
 
+/* ---- SNP-by-environment interaction (GEMMA's -gxe): for SNP g with rotated genotype x = U'x_g and rotated interaction
+ * xe = U'(x_g o e), the REML Wald test of xe in  y ~ W' + x + xe,  W' = the c shared covariates (the caller's W and U'e).
+ * Row g is by definition calculate(d, yr, [W', x], xe) of pg_assoc_dev's arithmetic with c + 1 covariates (decade scan,
+ * brentq + Newton, no grid): beta = beta_gxe, se, tau, lambda (float32), F (float64), pval = F(1, n - c - 2).sf(F) (may be NULL).
+ * Degenerate rows (constant x, xe in span([W', x]), a non-finite SNP, rank-deficient W') get NaN where calculate() does.
+ *   Wr n x c row-major, yr n, d n;  xr: p rows of n floats at row stride ldx >= n;  xer the same at ldxe >= n.
+ *   c = 1..PG_MAX_COVARIATES - 1 (else PG_ENOTSUP); n - c - 2 > 0 and non-NULL pointers (but pval, stats_dev), else PG_EINVAL.
+ *   pg_assoc_gxe_warm  : as pg_assoc_warm, for pg_assoc_gxe_dev with c shared covariates.
+ *   pg_gxe_scale_u_dev : Ue[i n + k] = e_i U[i ldU + k] (one float32 rounding; Ue dense n x n): U'(x o e) = Ue' x, so x o e is
+ *                        rotated by any rotation path of x with Ue (and its pg_geno_prep_dev image) in U's place. */
+int pg_assoc_gxe_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, const float *Wr, const float *yr,
+                     const float *xr, int64_t ldx, const float *xer, int64_t ldxe, float *beta, float *se, float *tau,
+                     float *lambda, double *F, double *pval, unsigned long long *stats_dev);
+int pg_assoc_gxe_warm(pg_ctx *ctx, int64_t n, int c);
+int pg_gxe_scale_u_dev(pg_ctx *ctx, int64_t n, const float *U, int64_t ldU, const float *e, float *Ue);
+
 /* host-pointer convenience: X in the REFERENCE layout (n x p row-major, already rotated), as
  * calculate() receives it; transposed to SNP-major on the device. */
 int pg_assoc(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, const float *Wr, const float *yr,

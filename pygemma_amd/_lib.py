@@ -25,6 +25,7 @@ SYMBOLS = [
     "pg_comm_group_end", "pgx_dgemm_dev", "pgx_sytrd_dev", "pgx_stedc_dev", "pgx_sb2_stage1_dev", "pgx_sb2_stage2_dev", "pgx_sb2_set_debug", "pg_kinship_geno_dev", "pg_assoc_lrt_dev", "pg_rotate_auto_dev", "pg_assoc_set_eval_trace", "pg_assoc_warm", "pg_rotate_auto_i8_dev",
     "pg_zkzt_dev", "pgx_dgemm_ex_dev", "pgx_ring_stamps", "pg_assoc_pheno_dev", "pg_assoc_pheno_warm", "pg_score_null_dev", "pg_score_dev",
     "pg_kinship_acc_bytes", "pg_kinship_bed_acc_dev", "pg_kinship_x_acc_dev", "pg_kinship_finish_dev",
+    "pg_assoc_gxe_dev", "pg_assoc_gxe_warm", "pg_gxe_scale_u_dev",
 ]
 
 
@@ -97,6 +98,12 @@ def load():
     L.pg_score_null_dev.restype = i32
     L.pg_score_dev.argtypes = [vp, i64, i32, i64, vp, vp, vp, C.c_float, vp, i64, vp, vp, vp, vp, vp, vp]
     L.pg_score_dev.restype = i32
+    L.pg_assoc_gxe_dev.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.pg_assoc_gxe_dev.restype = i32
+    L.pg_assoc_gxe_warm.argtypes = [vp, i64, i32]
+    L.pg_assoc_gxe_warm.restype = i32
+    L.pg_gxe_scale_u_dev.argtypes = [vp, i64, vp, i64, vp, vp]
+    L.pg_gxe_scale_u_dev.restype = i32
     L.pg_rotate_auto_i8_dev.argtypes = [vp, i64, i64, vp, vp, i32, i64, vp, i64, vp, vp]
     L.pg_rotate_auto_i8_dev.restype = i32
     L.pg_rotate_auto_dev.argtypes = [vp, i64, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp]

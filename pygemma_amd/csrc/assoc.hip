@@ -503,11 +503,20 @@ __device__ __forceinline__ void unpack_elem(const AssocParams &pr, const Elem<C>
     col[C] = e.x;
     col[C + 1] = buf[C + 1];
 }
+// The operands of one element as the Gram passes read them: EL::E (the element's registers), EL::Row (what addresses the SNP's
+// per-SNP columns), EL::load / EL::unpack.  WaldElem: the packed fixed row plus the SNP's x; the GxE scan has its own (GxeElem).
+template <int C> struct WaldElem {
+    using E = Elem<C>;
+    using Row = const float *;
+    template <bool HASX>
+    static __device__ __forceinline__ void load(const AssocParams &pr, Row xrow, int i, E &e) { load_elem<C, HASX>(pr, xrow, i, e); }
+    static __device__ __forceinline__ void unpack(const AssocParams &pr, const E &e, int i, float &d, float (&col)[C + 2]) { unpack_elem<C>(pr, e, i, d, col); }
+};
 
 // One pass over the n elements accumulating the level-0 Gram powers selected by MASK (1: P = W*'H^-1 W*,
 // 2: Q = W*'H^-2 W*, 4: R = W*'H^-3 W*; t1 rides with P, t2 with R), then the reduce-scatter to the owning lanes.
-template <int C, int MASK, bool HASX>
-__device__ __forceinline__ void gram_pass(const AssocParams &pr, const float *xrow, float lam, int lane, float *htab_out,
+template <int C, int MASK, bool HASX, class EL = WaldElem<C>>
+__device__ __forceinline__ void gram_pass(const AssocParams &pr, typename EL::Row xrow, float lam, int lane, float *htab_out,
                                           double (&Po)[Shape<C>::SLOTS], double (&Qo)[Shape<C>::SLOTS], double (&Ro)[Shape<C>::SLOTS],
                                           double &t1, double &t2)
 {
@@ -517,11 +526,12 @@ __device__ __forceinline__ void gram_pass(const AssocParams &pr, const float *xr
 #pragma unroll
     for (int k = 0; k < NP; k++) { if constexpr (DP) P[k] = 0.0; if constexpr (DQ) Q[k] = 0.0; if constexpr (DR) R[k] = 0.0; }
     double s1 = 0.0, s2 = 0.0;
-    pipelined<Elem<C>>(pr.niter, [&](Elem<C> &e, int it) { load_elem<C, HASX>(pr, xrow, it * 64 + lane, e); },
-                       [&](const Elem<C> &cur, int it) {
+    using E = typename EL::E;
+    pipelined<E>(pr.niter, [&](E &e, int it) { EL::template load<HASX>(pr, xrow, it * 64 + lane, e); },
+                       [&](const E &cur, int it) {
         const int i = it * 64 + lane;
         float d, colf[M];
-        unpack_elem<C>(pr, cur, i, d, colf);
+        EL::unpack(pr, cur, i, d, colf);
         const float h = hinv_f32(lam, d);        // pad rows: d = +inf -> h = 0
         if (htab_out) htab_out[i] = h;
         const double hd = (double)h;
@@ -556,8 +566,8 @@ __device__ __forceinline__ void gram_pass(const AssocParams &pr, const float *xr
 
 // One pass over the n elements for the entries of ONE slot and ONE power (PW = 1: P, 2: Q, 3: R): the per-entry arithmetic
 // and summation order are those of gram_pass (every entry is its own fma chain), only the grouping into passes differs.
-template <int C, int PW, int SL, bool HASX>
-__device__ __forceinline__ void gram_pass_slot(const AssocParams &pr, const float *xrow, float lam, int lane, float *htab_out, double &out, double &tsum)
+template <int C, int PW, int SL, bool HASX, class EL = WaldElem<C>>
+__device__ __forceinline__ void gram_pass_slot(const AssocParams &pr, typename EL::Row xrow, float lam, int lane, float *htab_out, double &out, double &tsum)
 {
     constexpr int M = Shape<C>::M, E0 = 64 * SL, NV = Shape<C>::slot_nv(SL), NVP = next_pow2(NV);
     double acc[NVP];
@@ -565,11 +575,12 @@ __device__ __forceinline__ void gram_pass_slot(const AssocParams &pr, const floa
     for (int k = 0; k < NVP; k++) acc[k] = 0.0;
     double s = 0.0;
     // wide rows (c > 20): one register set in flight instead of two, the element ring would push the slot's 64 accumulators to scratch
-    pipelined<Elem<C>, (M > 22 ? 1 : PFD)>(pr.niter, [&](Elem<C> &e, int it) { load_elem<C, HASX>(pr, xrow, it * 64 + lane, e); },
-                       [&](const Elem<C> &cur, int it) {
+    using E = typename EL::E;
+    pipelined<E, (M > 22 ? 1 : PFD)>(pr.niter, [&](E &e, int it) { EL::template load<HASX>(pr, xrow, it * 64 + lane, e); },
+                       [&](const E &cur, int it) {
         const int i = it * 64 + lane;
         float d, colf[M];
-        unpack_elem<C>(pr, cur, i, d, colf);
+        EL::unpack(pr, cur, i, d, colf);
         const float h = hinv_f32(lam, d);        // pad rows: d = +inf -> h = 0
         if (htab_out) htab_out[i] = h;
         const double hd = (double)h, h2 = hd * hd;
@@ -593,17 +604,17 @@ __device__ __forceinline__ void gram_pass_slot(const AssocParams &pr, const floa
     out = reduce_scatter<NVP>(acc, lane);
     if constexpr (SL == 0 && (PW == 1 || PW == 3)) tsum = bfly(s);
 }
-template <int C, int PW, bool HASX, int SL = 0>
-__device__ __forceinline__ void slot_passes(const AssocParams &pr, const float *xrow, float lam, int lane, float *htab_out,
+template <int C, int PW, bool HASX, int SL = 0, class EL = WaldElem<C>>
+__device__ __forceinline__ void slot_passes(const AssocParams &pr, typename EL::Row xrow, float lam, int lane, float *htab_out,
                                             double (&X)[Shape<C>::SLOTS], double &tsum)
 {
-    gram_pass_slot<C, PW, SL, HASX>(pr, xrow, lam, lane, SL == 0 ? htab_out : nullptr, X[SL], tsum);
-    if constexpr (SL + 1 < Shape<C>::SLOTS) slot_passes<C, PW, HASX, SL + 1>(pr, xrow, lam, lane, htab_out, X, tsum);
+    gram_pass_slot<C, PW, SL, HASX, EL>(pr, xrow, lam, lane, SL == 0 ? htab_out : nullptr, X[SL], tsum);
+    if constexpr (SL + 1 < Shape<C>::SLOTS) slot_passes<C, PW, HASX, SL + 1, EL>(pr, xrow, lam, lane, htab_out, X, tsum);
 }
 
 // Level-0 Grams at an arbitrary lambda, then the sweeps.
-template <int C, bool FULL>
-__device__ __forceinline__ void eval_specific(const AssocParams &pr, const float *xrow, float lam, int lane, const Own<C> &own, EvalOut &o,
+template <int C, bool FULL, class EL = WaldElem<C>>
+__device__ __forceinline__ void eval_specific(const AssocParams &pr, typename EL::Row xrow, float lam, int lane, const Own<C> &own, EvalOut &o,
                                               double *piv)
 {
     constexpr int SLOTS = Shape<C>::SLOTS;
@@ -612,18 +623,18 @@ __device__ __forceinline__ void eval_specific(const AssocParams &pr, const float
     for (int sl = 0; sl < SLOTS; sl++) R[sl] = 0.0;
     if constexpr (Shape<C>::CHUNKED) {
         double tq = 0.0;
-        slot_passes<C, 1, true>(pr, xrow, lam, lane, nullptr, P, t1);
-        slot_passes<C, 2, true>(pr, xrow, lam, lane, nullptr, Q, tq);
-        if (FULL) slot_passes<C, 3, true>(pr, xrow, lam, lane, nullptr, R, t2);
+        slot_passes<C, 1, true, 0, EL>(pr, xrow, lam, lane, nullptr, P, t1);
+        slot_passes<C, 2, true, 0, EL>(pr, xrow, lam, lane, nullptr, Q, tq);
+        if (FULL) slot_passes<C, 3, true, 0, EL>(pr, xrow, lam, lane, nullptr, R, t2);
     } else if constexpr (FULL && Shape<C>::FUSE_PQR) {
-        gram_pass<C, 7, true>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+        gram_pass<C, 7, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
     } else if constexpr (Shape<C>::FUSE_PQ) {
-        gram_pass<C, 3, true>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
-        if (FULL) gram_pass<C, 4, true>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+        gram_pass<C, 3, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+        if (FULL) gram_pass<C, 4, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
     } else {
-        gram_pass<C, 1, true>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
-        gram_pass<C, 2, true>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
-        if (FULL) gram_pass<C, 4, true>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+        gram_pass<C, 1, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+        gram_pass<C, 2, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+        if (FULL) gram_pass<C, 4, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
     }
     lane_sweeps<C, FULL>(P, Q, R, own, t1, t2, lane, o, piv);
 }
@@ -1069,6 +1080,256 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
 }
 
 // ------------------------------------------------------------------------------------------------
+// GxE (pg_assoc_gxe_dev): the REML Wald test of x o e with the SNP's own x among the covariates.  The full model has C = CS + 1
+// covariates — the CS shared ones W' = [W, e] of the packed fixed rows and the per-SNP x — and the tested column xe, so the Gram
+// matrices are those of Shape<CS + 1> over the columns [W' | x | xe | y], swept by lane_sweeps<CS + 1> exactly as the Wald kernel
+// sweeps [W | x | y] with CS + 1 covariates: a row is what oracle calculate(d, y, [W', x], xe) gives in the kernels' order.
+// The fixed block [W', y] at the decade lambdas is setup_tabs_kernel<CS>'s output on the same fixed rows (its row y is row CS + 1
+// there); per SNP the decade scan accumulates only the NE = 2 CS + 5 entries per power that involve x or xe.
+#if defined(PG_ASSOC_PART) && (PG_ASSOC_PART == 6 || PG_ASSOC_PART == 7)
+struct GxeRows { const float *x, *xe; };   // the SNP's rotated x and x o e
+template <int CS> struct GxeVals {
+    static constexpr int S4 = (CS + 2 + 3) / 4;
+    float4 row[S4];
+    float x, xe;
+};
+// element operands of the Gram passes at the C = CS + 1 covariates of the full model: columns w_0..w_{CS-1}, x, xe, y
+template <int C> struct GxeElem {
+    static constexpr int CS = C - 1;
+    using E = GxeVals<CS>;
+    using Row = GxeRows;
+    template <bool HASX>
+    static __device__ __forceinline__ void load(const AssocParams &pr, Row r, int i, E &e)
+    {   // as load_elem: unconditional loads, pad rows have d = +inf (h = 0), the per-SNP index clamped to n - 1
+        const float4 *src = reinterpret_cast<const float4 *>(pr.fixed + (size_t)i * pr.rowf);
+#pragma unroll
+        for (int k = 0; k < E::S4; k++) e.row[k] = src[k];
+        const int ic = min(i, pr.n - 1);
+        e.x = r.x[ic];
+        e.xe = r.xe[ic];
+    }
+    static __device__ __forceinline__ void unpack(const AssocParams &pr, const E &e, int i, float &d, float (&col)[C + 2])
+    {
+        float buf[4 * E::S4];
+#pragma unroll
+        for (int k = 0; k < E::S4; k++) {
+            buf[4 * k] = e.row[k].x; buf[4 * k + 1] = e.row[k].y; buf[4 * k + 2] = e.row[k].z; buf[4 * k + 3] = e.row[k].w;
+        }
+        d = buf[0];
+#pragma unroll
+        for (int j = 0; j < CS; j++) col[j] = buf[1 + j];
+        col[CS] = e.x;
+        col[CS + 1] = e.xe;
+        col[CS + 2] = buf[CS + 1];
+    }
+};
+template <int CS> struct GxeShape {
+    static constexpr int C = CS + 1, NE = 2 * CS + 5;   // scan entries per power: x.w_k, x.x, xe.w_k, xe.x, xe.xe, y.x, y.xe
+    // lambdas per scan pass as in the multi-phenotype scan: the accumulators plus the NE products held across them within SCAN_NV;
+    // rows wider than PG_PHENO_SPLIT_XE (CS >= 11) take one power per pass
+    static constexpr int PWS = NE > PG_PHENO_SPLIT_XE ? 1 : 2;
+    static constexpr int G0 = (Shape<C>::SCAN_NV - NE) / (PWS * NE), G = G0 < 1 ? 1 : (G0 > NLAM ? NLAM : G0);
+};
+// per-wave dynamic LDS of assoc_gxe_kernel: [piv: 3 M doubles when the sweeps go through LDS] | xent[NLAM][2][NE] doubles |
+// evs[NLAM] | d1s[NLAM] | lls[NLAM] | vals[n_vals]
+__host__ __device__ constexpr size_t gxe_per_wave_bytes(int M, bool sweep_lds, int NE, size_t evalout_bytes, int n_vals)
+{
+    return (((sweep_lds ? (size_t)3 * M * 8 : 0) + (size_t)NLAM * 2 * NE * 8 + NLAM * evalout_bytes + 2 * NLAM * 4 + (size_t)n_vals * 4) + 15) & ~(size_t)15;
+}
+
+// GG decade lambdas, PWS powers from PW0 (2, 0: P and Q; 1, pw: one of them) of the NE x / xe entries into xent [NLAM][2][NE].
+// z_k are exact f64 products of two f32 columns, so fma(h, z_k) and fma(h^2, z_k) add what the Gram pass of a specific lambda adds
+// for the same entry (see scan_accumulate); every value goes through reduce_scatter: same bits as a full Gram pass.
+template <int CS, int GG, int PWS, int PW0>
+__device__ __forceinline__ void gxe_scan_accumulate(const AssocParams &pr, GxeRows xr, int t0, int lane, double *out)
+{
+    using EL = GxeElem<CS + 1>;
+    constexpr int M = CS + 3, NE = GxeShape<CS>::NE, NV = GG * PWS * NE;
+    auto dest = [&](int v) { const int gg = v / (PWS * NE), r = v - gg * PWS * NE; return (t0 + gg) * 2 * NE + PW0 * NE + r; };
+    constexpr int NV0 = NV < 64 ? NV : 64, NV1 = NV > 64 ? NV - 64 : 0;
+    constexpr int NVP0 = next_pow2(NV0), NVP1 = next_pow2(NV1 > 0 ? NV1 : 1);
+    static_assert(NV <= 128, "scan group too large");
+    double acc[NV0 == 64 ? 64 + NVP1 : NVP0];
+#pragma unroll
+    for (int k = 0; k < (NV0 == 64 ? 64 + NVP1 : NVP0); k++) acc[k] = 0.0;
+    struct SE { typename EL::E e; float h[GG]; };
+    pipelined<SE>(pr.niter, [&](SE &q, int it) {
+        const int i = it * 64 + lane;
+        EL::template load<true>(pr, xr, i, q.e);
+#pragma unroll
+        for (int g = 0; g < GG; g++) q.h[g] = pr.htab[(size_t)(t0 + g) * pr.npad + i];
+    }, [&](const SE &q, int it) {
+        const int i = it * 64 + lane;
+        float d, colf[M];
+        EL::unpack(pr, q.e, i, d, colf);
+        const double xd = (double)colf[CS], ed = (double)colf[CS + 1], yd = (double)colf[CS + 2];
+        double z[NE];
+#pragma unroll
+        for (int k = 0; k < CS; k++) { z[k] = xd * (double)colf[k]; z[CS + 1 + k] = ed * (double)colf[k]; }
+        z[CS] = xd * xd;
+        z[2 * CS + 1] = ed * xd;
+        z[2 * CS + 2] = ed * ed;
+        z[2 * CS + 3] = yd * xd;
+        z[2 * CS + 4] = yd * ed;
+#pragma unroll
+        for (int g = 0; g < GG; g++) {
+            const double hd = (double)q.h[g];
+            const double h2 = hd * hd;
+#pragma unroll
+            for (int k = 0; k < NE; k++) {
+                if constexpr (PWS == 2) {
+                    acc[g * 2 * NE + k] = fma(hd, z[k], acc[g * 2 * NE + k]);
+                    acc[g * 2 * NE + NE + k] = fma(h2, z[k], acc[g * 2 * NE + NE + k]);
+                } else {
+                    acc[g * NE + k] = fma(PW0 == 0 ? hd : h2, z[k], acc[g * NE + k]);
+                }
+            }
+        }
+    });
+    {
+        double t[NVP0];
+#pragma unroll
+        for (int k = 0; k < NVP0; k++) t[k] = acc[k];
+        const double tot = reduce_scatter<NVP0>(t, lane);
+        const int idx = lane % NVP0;
+        if (idx < NV0 && lane < NVP0) out[dest(idx)] = tot;
+    }
+    if constexpr (NV1 > 0) {
+        double t[NVP1];
+#pragma unroll
+        for (int k = 0; k < NVP1; k++) t[k] = acc[64 + k];
+        const double tot = reduce_scatter<NVP1>(t, lane);
+        const int idx = lane % NVP1;
+        if (idx < NV1 && lane < NVP1) out[dest(64 + idx)] = tot;
+    }
+}
+template <int CS, int T0>
+__device__ __forceinline__ void gxe_scan_all(const AssocParams &pr, GxeRows xr, int lane, double *xent)
+{
+    constexpr int G = GxeShape<CS>::G;
+    if constexpr (T0 < NLAM) {
+        constexpr int GG = (NLAM - T0) < G ? (NLAM - T0) : G;
+        if constexpr (GxeShape<CS>::PWS == 2) {
+            gxe_scan_accumulate<CS, GG, 2, 0>(pr, xr, T0, lane, xent);
+        } else {
+            gxe_scan_accumulate<CS, GG, 1, 0>(pr, xr, T0, lane, xent);
+            gxe_scan_accumulate<CS, GG, 1, 1>(pr, xr, T0, lane, xent);
+        }
+        gxe_scan_all<CS, T0 + GG>(pr, xr, lane, xent);
+    }
+}
+
+// One wavefront per SNP, WPB per workgroup; the REML search of assoc_kernel (Brent + Newton, no grid) on the full model's Grams.
+template <int CS>
+__global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_gxe_kernel(AssocParams pr, const float *xer, long long ldxe)
+{
+    constexpr int C = CS + 1, M = Shape<C>::M, SLOTS = Shape<C>::SLOTS, NE = GxeShape<CS>::NE, NPS = Shape<CS>::NP;
+    using EL = GxeElem<C>;
+    extern __shared__ unsigned char smem[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long g = (long long)blockIdx.x * WPB + wave;
+    if (g >= pr.p) return;  // whole wavefront leaves; no workgroup barrier is used anywhere in this kernel
+    constexpr size_t piv_bytes = Shape<C>::SWEEP_LDS ? (size_t)3 * M * 8 : 0;
+    unsigned char *base = smem + (size_t)wave * gxe_per_wave_bytes(M, Shape<C>::SWEEP_LDS, NE, sizeof(EvalOut), pr.n_vals);
+    double *piv = reinterpret_cast<double *>(base);
+    base += piv_bytes;
+    double *xent = reinterpret_cast<double *>(base);
+    EvalOut *evs = reinterpret_cast<EvalOut *>(base + (size_t)NLAM * 2 * NE * 8);
+    float *d1s = reinterpret_cast<float *>(evs + NLAM);
+    float *lls = d1s + NLAM;
+    float *vals = lls + NLAM;
+    const GxeRows xr{pr.xr + (size_t)g * pr.ldx, xer + (size_t)g * ldxe};
+
+    Own<C> own;
+    own.init(lane);
+    // ---- decade scan: the x / xe entries at the 11 shared lambdas
+    gxe_scan_all<CS, 0>(pr, xr, lane, xent);
+    wave_lds_sync();
+    for (int t = 0; t < NLAM; t++) {
+        double P[SLOTS], Q[SLOTS], R[SLOTS];
+        const double *fp = pr.fixg + ((size_t)t * 2 + 0) * NPS, *fq = pr.fixg + ((size_t)t * 2 + 1) * NPS;
+        const double *xe = xent + t * 2 * NE;
+#pragma unroll
+        for (int sl = 0; sl < SLOTS; sl++) {
+            const int r = own.r[sl], c = own.c[sl];
+            // rows x (CS) and xe (CS + 1) and the entries (y, x), (y, xe) come from the scan; W' and y from setup_tabs_kernel<CS>,
+            // whose row y is row CS + 1
+            const int k = (r == CS) ? c : (r == CS + 1) ? CS + 1 + c : (r == CS + 2 && c == CS) ? 2 * CS + 3 : (r == CS + 2 && c == CS + 1) ? 2 * CS + 4 : -1;
+            const int f = (r < CS) ? tri(r, c) : tri(CS + 1, c < CS ? c : CS + 1);
+            const int kk = k >= 0 ? k : 0;
+            P[sl] = k >= 0 ? xe[kk] : fp[f];
+            Q[sl] = k >= 0 ? xe[NE + kk] : fq[f];
+            R[sl] = 0.0;
+        }
+        EvalOut e;
+        lane_sweeps<C, false>(P, Q, R, own, pr.t1tab[t], 0.0, lane, e, piv);
+        if (lane == 0) {
+            evs[t] = e;
+            d1s[t] = d1_f(pr, pr.lam11[t], e.yPy, e.yPPy, e.trP);
+            lls[t] = logl_f(pr, e.yPy, pr.ldHtab[t], e.ld);
+        }
+    }
+    wave_lds_sync();
+    // ---- candidate selection, Brent + Newton: assoc_kernel's (pyx:144-192)
+    float best_l = lls[0], best_lambda;
+    EvalOut best_e;
+    if (best_l < lls[NLAM - 1]) { best_l = lls[NLAM - 1]; best_lambda = pr.lam11[NLAM - 1]; best_e = evs[NLAM - 1]; }
+    else { best_lambda = pr.lam11[0]; best_e = evs[0]; }
+    unsigned n_fast = 0, n_full = 0;
+    for (int k = 0; k < NLAM - 1; k++) {
+        const float f0 = d1s[k], f1 = d1s[k + 1];
+        if (__builtin_signbit(f0) == __builtin_signbit(f1)) continue;
+        const float l0 = pr.lam11[k], l1 = pr.lam11[k + 1];
+        double root = brentq_dev(
+            [&](double x) -> double {
+                EvalOut e;
+                const float lf = (float)x;
+                eval_specific<C, false, EL>(pr, xr, lf, lane, own, e, piv);
+                n_fast++;
+                return (double)d1_f(pr, lf, e.yPy, e.yPPy, e.trP);
+            },
+            (double)l0, (double)l1, (double)f0, (double)f1);
+        const float lroot = newton_dev(pr, (float)root, l0, l1, [&](float lf, EvalOut &e) {
+            eval_specific<C, true, EL>(pr, xr, lf, lane, own, e, piv);
+            n_full++;
+        });
+        EvalOut e;
+        eval_specific<C, false, EL>(pr, xr, lroot, lane, own, e, piv);
+        n_fast++;
+        const float ldH = device_logdet_H(pr, lroot, lane, vals);
+        const float ll = logl_f(pr, e.yPy, ldH, e.ld);
+        if (ll > best_l) { best_l = ll; best_lambda = lroot; best_e = e; }
+    }
+    // ---- beta_gxe, se, tau, F (pyx:1529-1537, lmm.py:471): the tested column is xe, the last one before y
+    if (lane == 0) {
+        const float b = __fdiv_rn(best_e.Pyx_c, best_e.Pxx_c);
+        const float pxx = (PG_MINV > best_e.Pxx_c) ? PG_MINV : best_e.Pxx_c;
+        const float sb = (float)(__dsqrt_rn((double)best_e.yPy) / ((double)sqrtf(pxx) * __dsqrt_rn((double)(pr.nu))));
+        const float ta = __fdiv_rn((float)pr.nu, best_e.yPy);
+        const double t = (double)__fdiv_rn(b, sb);
+        pr.beta[g] = b; pr.se[g] = sb; pr.tau[g] = ta; pr.lam[g] = best_lambda; pr.F[g] = t * t;
+        if (pr.stats) { atomicAdd(&pr.stats[0], (unsigned long long)n_fast); atomicAdd(&pr.stats[1], (unsigned long long)n_full); }
+    }
+}
+
+template <int CS>
+static int launch_gxe(pg_ctx *ctx, AssocParams &pr, const float *xer, long long ldxe)
+{
+    constexpr int C = CS + 1;
+    const size_t lds = (size_t)WPB * gxe_per_wave_bytes(Shape<C>::M, Shape<C>::SWEEP_LDS, GxeShape<CS>::NE, sizeof(EvalOut), pr.n_vals);
+    PG_REQUIRE(pr.n_vals >= 0 && lds <= 160 * 1024, "assoc_gxe: c = %d, n_vals = %d need %zu bytes of LDS per workgroup", CS, pr.n_vals, lds);
+    setup_tabs_kernel<CS><<<NLAM, 64, (size_t)pr.n_vals * 4 + 16, ctx->stream>>>(pr);
+    PG_HIP(hipGetLastError());
+    if (lds > 64 * 1024)
+        PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&assoc_gxe_kernel<CS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long long nblk = (pr.p + WPB - 1) / WPB;
+    assoc_gxe_kernel<CS><<<dim3((unsigned)nblk), 64 * WPB, lds, ctx->stream>>>(pr, xer, ldxe);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+#endif
+
+// ------------------------------------------------------------------------------------------------
 // host side
 template <int C, bool LRT = false>
 static int launch_assoc(pg_ctx *ctx, AssocParams &pr)
@@ -1136,9 +1397,46 @@ int launch_assoc_lrt_hi(pg_ctx *ctx, AssocParams &pr);
 //   assoc_pheno.hip    multi-phenotype kernels (pg_assoc_pheno_dev), c = 1..15     assoc_pheno_hi.hip  c = 16..PG_MAX_COVARIATES
 int launch_assoc_pheno(pg_ctx *ctx, AssocParams &pr, const PhenoLaunch &pl);
 int launch_assoc_pheno_hi(pg_ctx *ctx, AssocParams &pr, const PhenoLaunch &pl);
+//   assoc_gxe.hip      GxE kernels (pg_assoc_gxe_dev), shared c = 1..15            assoc_gxe_hi.hip    c = 16..PG_MAX_COVARIATES - 1
+int launch_assoc_gxe(pg_ctx *ctx, AssocParams &pr, const float *xer, long long ldxe);
+int launch_assoc_gxe_hi(pg_ctx *ctx, AssocParams &pr, const float *xer, long long ldxe);
 #define PG_CASE(CC) case CC: return launch_assoc<CC, PG_CASE_LRT>(ctx, pr);
 #define PG_PCASE(CC) case CC: return launch_pheno<CC>(ctx, pr, pl);
-#if defined(PG_ASSOC_PART) && PG_ASSOC_PART == 4
+#define PG_GCASE(CC) case CC: return launch_gxe<CC>(ctx, pr, xer, ldxe);
+#if defined(PG_ASSOC_PART) && PG_ASSOC_PART == 6
+int launch_assoc_gxe(pg_ctx *ctx, AssocParams &pr, const float *xer, long long ldxe)
+{
+    switch (pr.c) {
+        PG_GCASE(1) PG_GCASE(2) PG_GCASE(3) PG_GCASE(4) PG_GCASE(5) PG_GCASE(6) PG_GCASE(7) PG_GCASE(8) PG_GCASE(9) PG_GCASE(10)
+        PG_GCASE(11) PG_GCASE(12) PG_GCASE(13) PG_GCASE(14) PG_GCASE(15)
+        default: return launch_assoc_gxe_hi(ctx, pr, xer, ldxe);
+    }
+}
+// Ue[i, k] = e_i U[i, k] (one f32 rounding): U'(e o x) = (diag(e) U)' x, so every rotation path of x gives x o e from Ue
+__global__ __launch_bounds__(256) void gxe_scale_u_kernel(long long n, const float *U, long long ldU, const float *e, float *Ue)
+{
+    const long long i = blockIdx.y, k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && k < n) Ue[i * n + k] = __fmul_rn(e[i], U[i * ldU + k]);
+}
+extern "C" int pg_gxe_scale_u_dev(pg_ctx *ctx, int64_t n, const float *U, int64_t ldU, const float *e, float *Ue)
+{
+    PG_REQUIRE(ctx && U && e && Ue, "pg_gxe_scale_u_dev: NULL argument");
+    PG_REQUIRE(n >= 1 && n < (1LL << 30) && ldU >= n, "pg_gxe_scale_u_dev: bad shape n=%lld ldU=%lld", (long long)n, (long long)ldU);
+    PG_HIP(hipSetDevice(ctx->device));
+    gxe_scale_u_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)n), 256, 0, ctx->stream>>>(n, U, ldU, e, Ue);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+#elif defined(PG_ASSOC_PART) && PG_ASSOC_PART == 7
+int launch_assoc_gxe_hi(pg_ctx *ctx, AssocParams &pr, const float *xer, long long ldxe)
+{
+    switch (pr.c) {
+        PG_GCASE(16) PG_GCASE(17) PG_GCASE(18) PG_GCASE(19) PG_GCASE(20) PG_GCASE(21) PG_GCASE(22) PG_GCASE(23) PG_GCASE(24) PG_GCASE(25)
+        PG_GCASE(26) PG_GCASE(27) PG_GCASE(28) PG_GCASE(29)
+        default: return PG_ENOTSUP;
+    }
+}
+#elif defined(PG_ASSOC_PART) && PG_ASSOC_PART == 4
 int launch_assoc_pheno(pg_ctx *ctx, AssocParams &pr, const PhenoLaunch &pl)
 {
     switch (pr.c) {
@@ -1214,6 +1512,7 @@ int launch_assoc_pheno(pg_ctx *, AssocParams &, const PhenoLaunch &) { return PG
 #endif
 #undef PG_CASE
 #undef PG_PCASE
+#undef PG_GCASE
 
 #ifndef PG_ASSOC_PART
 // ------------------------------------------------------------------------------------------------
@@ -1710,6 +2009,62 @@ extern "C" int pg_assoc_pheno_warm(pg_ctx *ctx, int64_t n, int c, int t, int64_t
     int rc = build_npsum_plan(ctx, n);
     if (rc) return rc;
     return ensure(ctx, &ctx->pheno, &ctx->pheno_bytes, pheno_layout(n, c, t, p).bytes);
+}
+
+// ---- GxE: the Wald test of x o e with x among the covariates (assoc_gxe_kernel).  c shared covariates Wr (n x c: W and e in the
+// eigenbasis), per SNP the rotated x (row stride ldx) and x o e (ldxe); p-values from F(1, n - c - 2).
+extern "C" int pg_assoc_gxe_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, const float *Wr, const float *yr,
+                                const float *xr, int64_t ldx, const float *xer, int64_t ldxe, float *beta, float *se, float *tau,
+                                float *lambda, double *F, double *pval, unsigned long long *stats_dev)
+{
+    PG_REQUIRE(ctx && d && Wr && yr && xr && xer && beta && se && tau && lambda && F, "pg_assoc_gxe_dev: NULL argument");
+    PG_REQUIRE(n >= 2 && n < (1LL << 30) && p >= 0 && ldx >= n && ldxe >= n, "pg_assoc_gxe_dev: bad shape n=%lld p=%lld ldx=%lld ldxe=%lld",
+               (long long)n, (long long)p, (long long)ldx, (long long)ldxe);
+    if (c < 1 || c + 1 > PG_MAX_COVARIATES) {
+        set_error("pg_assoc_gxe_dev: c=%d shared covariates not supported by this build (1..%d)", c, PG_MAX_COVARIATES - 1);
+        return PG_ENOTSUP;
+    }
+    PG_REQUIRE(n - c - 2 > 0, "pg_assoc_gxe_dev: n - c - 2 must be positive");
+    if (p == 0) return PG_OK;
+    PG_HIP(hipSetDevice(ctx->device));
+    int rc = build_npsum_plan(ctx, n);
+    if (rc) return rc;
+    AssocParams pr{};
+    fill_params(ctx, n, c + 1, 0, pr);                 // the full model: c + 1 covariates (nu = n - c - 2, the likelihood constants)
+    pr.c = c; pr.rowf = ((c + 2 + 3) / 4) * 4;         // ... over the fixed rows [d, W', y] of the c shared ones
+    pr.p = p; pr.ldx = ldx; pr.xr = xr;
+    const int NP = (c + 2) * (c + 3) / 2;
+    rc = ensure(ctx, &ctx->fixed, &ctx->fixed_bytes, (size_t)pr.npad * pr.rowf * 4);
+    if (rc) return rc;
+    const size_t off_fixg = ((size_t)NLAM * pr.npad * 4 + 255) & ~(size_t)255;
+    const size_t off_t1 = off_fixg + (size_t)NLAM * 2 * NP * 8;
+    const size_t off_ldh = off_t1 + NLAM * 8;
+    rc = ensure(ctx, &ctx->tabs, &ctx->tabs_bytes, off_ldh + NLAM * 4 + 256);
+    if (rc) return rc;
+    pr.fixed = (const float *)ctx->fixed;
+    pr.htab = (float *)ctx->tabs;
+    pr.fixg = (double *)((char *)ctx->tabs + off_fixg);
+    pr.t1tab = (double *)((char *)ctx->tabs + off_t1);
+    pr.ldHtab = (float *)((char *)ctx->tabs + off_ldh);
+    pr.beta = beta; pr.se = se; pr.tau = tau; pr.lam = lambda; pr.F = F;
+    pr.stats = stats_dev;
+    build_fixed_kernel<<<(pr.npad + 255) / 256, 256, 0, ctx->stream>>>(pr.n, pr.npad, c, c, pr.rowf, d, Wr, yr, (float *)ctx->fixed);
+    PG_HIP(hipGetLastError());
+    rc = launch_assoc_gxe(ctx, pr, xer, ldxe);
+    if (rc) return rc;
+    if (pval) return pg_fdist_sf_dev(ctx, p, F, (double)(n - c - 2), pval);
+    return PG_OK;
+}
+
+// pg_assoc_warm for pg_assoc_gxe_dev (the fixed rows and tables have the shape of c shared covariates)
+extern "C" int pg_assoc_gxe_warm(pg_ctx *ctx, int64_t n, int c)
+{
+    PG_REQUIRE(ctx && n >= 2 && n < (1LL << 30), "pg_assoc_gxe_warm: bad arguments");
+    if (c < 1 || c + 1 > PG_MAX_COVARIATES) {
+        set_error("pg_assoc_gxe_warm: c=%d shared covariates not supported by this build (1..%d)", c, PG_MAX_COVARIATES - 1);
+        return PG_ENOTSUP;
+    }
+    return pg_assoc_warm(ctx, n, c);
 }
 
 namespace pg {

@@ -38,7 +38,7 @@ from .bed import PackedBed
 from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_restricted, newton, the *_overload scalars)
 from . import model as _model
 
-__all__ = ["pygemma", "pygemma_multi", "pygemma_score", "SampleIter", "pinned_empty", "pin", "kinship"] + _model.__all__
+__all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "SampleIter", "pinned_empty", "pin", "kinship"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -164,10 +164,12 @@ def _put_window(ctx, src, s, e, dst, dpitch=None, staging=None, threads=_STAGE_T
         _lib.check(L.pg_memcpy2d_h2d_async(ctx.handle, dst, dpitch, ptr, spitch, width, rows), "pg_memcpy2d_h2d_async")
 
 
-def _batch_geometry(n, a, b):
-    """(SNPs per batch, row pitch in elements of a raw sample-major batch) for the block [a, b) of one GPU."""
+def _batch_geometry(n, a, b, gxe=False):
+    """(SNPs per batch, row pitch in elements of a raw sample-major batch) for the block [a, b) of one GPU (`gxe`: the interaction
+    scan, whose batches also hold the rotated x o e block)."""
     ldx = (n + 63) // 64 * 64
-    pb_max = max(256, int(_BATCH_BYTES // (12 * ldx)) // 256 * 256)   # raw block + rotated block + two fp16 planes
+    per_snp = (16 if gxe else 12) * ldx                               # raw block + rotated block + two fp16 planes [+ rotated x o e]
+    pb_max = max(256, int(_BATCH_BYTES // per_snp) // 256 * 256)
     pb_max = min(pb_max, _BATCH_SNPS, b - a)
     nbat = max(-(-(b - a) // pb_max), min(_BATCH_COUNT, -(-(b - a) // _BATCH_MIN)))
     pb_max = min(pb_max, (-(-(b - a) // nbat) + 255) // 256 * 256)
@@ -189,7 +191,7 @@ class _Prefetch:
     buffers.  The SNP loop then takes those batches instead of issuing the copies: the loop runs at the kernels' rate, and at
     288 GB of HBM a 40 GB float32 X is resident before U is."""
 
-    def __init__(self, L, X, blocks, n, esz, verbose):
+    def __init__(self, L, X, blocks, n, esz, verbose, gxe=False):
         self.L, self.X, self.n, self.esz, self.verbose = L, X, n, esz, verbose
         self.lock = threading.Lock()
         self.ready = [dict() for _ in blocks]
@@ -198,7 +200,7 @@ class _Prefetch:
         self.stop = False                        # set when the eigensolver is done: the batch in flight is the last one
         self.threads = []
         try:
-            self._plan(blocks, n, esz)
+            self._plan(blocks, n, esz, gxe)
         except BaseException:                    # a context or buffer of GPU g failed: release those of the GPUs before it
             for ctx in self.ctxs:
                 ctx.close()
@@ -208,14 +210,16 @@ class _Prefetch:
         for th in self.threads:
             th.start()
 
-    def _plan(self, blocks, n, esz):
+    def _plan(self, blocks, n, esz, gxe):
         for g, (a, b) in enumerate(blocks):
             ctx = _lib.Context(g)
             self.ctxs.append(ctx)
             free, _total = ctx.mem_info()
             reserve = (96 * n * n if g == 0 else 12 * n * n) + 2 * _BATCH_BYTES + _PREFETCH_MARGIN      # GPU 0: the eigensolver's 10 n^2 doubles + its outputs
+            if gxe:                                  # diag(e) U and its genotype prep beside U's (the x o e slices are in _BATCH_BYTES)
+                reserve += 4 * n * n + int(self.L.pg_geno_prep_bytes(n))
             budget = min(free - reserve, _PREFETCH_MAX)
-            pb_max, ldX = _batch_geometry(n, a, b)
+            pb_max, ldX = _batch_geometry(n, a, b, gxe)
             per = n * ldX * esz
             batches = [(s, min(s + pb_max, b)) for s in range(a, b, pb_max)]
             batches = batches[: max(0, int(budget // per))]
@@ -266,11 +270,12 @@ class _Prefetch:
 _Mode = namedtuple("_Mode", "cols nout warm launch decode")
 
 
-def _scan_mode(L, n, c, grid, lrt, npheno, lam0):
-    """The Wald scan (with `lrt` plus the likelihood-ratio columns), the scan of `npheno` > 0 phenotypes, or the score scan at the
-    null model's float32 ML lambda `lam0` (the same for every GPU).  Each writes the 32-byte rows [F | p | beta | se | tau | lambda]
-    of dist.result_columns, for npheno phenotype-major rows of pb SNPs with npheno; lrt appends [l_alt | l_null | D_lrt | p_lrt]
-    in float64."""
+def _scan_mode(L, n, c, grid, lrt, npheno, lam0, gxe=False):
+    """The Wald scan (with `lrt` plus the likelihood-ratio columns), the scan of `npheno` > 0 phenotypes, the score scan at the
+    null model's float32 ML lambda `lam0` (the same for every GPU), or with `gxe` the interaction scan (c shared covariates, the
+    last of them e; its launch takes the rotated x o e block as a sixth argument).  Each writes the 32-byte rows
+    [F | p | beta | se | tau | lambda] of dist.result_columns, for npheno phenotype-major rows of pb SNPs with npheno; lrt appends
+    [l_alt | l_null | D_lrt | p_lrt] in float64."""
     ldx = (n + 63) // 64 * 64
     t = npheno or 1
 
@@ -285,6 +290,12 @@ def _scan_mode(L, n, c, grid, lrt, npheno, lam0):
         def launch(ctx, dev, pb, dXr, r0):
             _lib.check(L.pg_assoc_pheno_dev(ctx.handle, n, c, pb, npheno, *dev, n, dXr, ldx, int(grid), *rows(r0, npheno * pb), None),
                        "pg_assoc_pheno_dev")
+    elif gxe:
+        def warm(ctx, pb_max):
+            _lib.check(L.pg_assoc_gxe_warm(ctx.handle, n, c), "pg_assoc_gxe_warm")
+
+        def launch(ctx, dev, pb, dXr, r0, dXEr):
+            _lib.check(L.pg_assoc_gxe_dev(ctx.handle, n, c, pb, *dev, dXr, ldx, dXEr, ldx, *rows(r0, pb), None), "pg_assoc_gxe_dev")
     elif lam0 is not None:
         def launch(ctx, dev, pb, dXr, r0):
             _lib.check(L.pg_score_dev(ctx.handle, n, c, pb, *dev, float(lam0), dXr, ldx, *rows(r0, pb)), "pg_score_dev")
@@ -313,8 +324,9 @@ def _scan_mode(L, n, c, grid, lrt, npheno, lam0):
 
 # The per-call invariants every GPU's block of a scan reads: eigenvalues d, rotated covariates Wr (n, c), rotated phenotype yr ((n,),
 # or (npheno, n) phenotype-major rows), X as _scan leaves it, the _Mode, the checkpoint directory, the stats dict, the _Prefetch
-# (each or None), the result columns `out` (filled in place) and `errs`, where the block and worker threads leave their exceptions
-_Job = namedtuple("_Job", "n c d Wr yr X grid eigen mode ckpt stats pre verbose out errs")
+# (each or None), the result columns `out` (filled in place) and `errs`, where the block and worker threads leave their exceptions, and
+# for the interaction scan the float32 environment `e` (n,) (None otherwise)
+_Job = namedtuple("_Job", "n c d Wr yr X grid eigen mode ckpt stats pre verbose out errs e", defaults=(None,))
 
 
 def _restore(job, device, a, b, pb_max):
@@ -369,13 +381,21 @@ def _run_block(job, device, a, b, dU, comm):
                 # genotype fast path of the rotation (<= 3 equally spaced values per column), fp32 MFMA otherwise
                 dprep = ctx0.alloc(L.pg_geno_prep_bytes(n))
                 _lib.check(L.pg_geno_prep_dev(ctx0.handle, n, dU.ptr, n, dprep.ptr), "pg_geno_prep_dev")
+            gxe = job.e is not None
+            if gxe:
+                # U'(x o e) = (diag(e) U)' x: Ue and its genotype prep, made on this GPU (after the broadcast of U), and every batch
+                # rotated twice, with (U, prep) into Xr and with (Ue, prep_e) into XEr
+                dE = ctx0.to_device(job.e)
+                dUe, dprepe = ctx0.alloc(n * n * 4), ctx0.alloc(L.pg_geno_prep_bytes(n))
+                _lib.check(L.pg_gxe_scale_u_dev(ctx0.handle, n, dU.ptr, n, dE.ptr, dUe.ptr), "pg_gxe_scale_u_dev")
+                _lib.check(L.pg_geno_prep_dev(ctx0.handle, n, dUe.ptr, n, dprepe.ptr), "pg_geno_prep_dev")
             ctx0.sync()
             packed = isinstance(X, PackedBed)
             x8 = (not packed) and X.dtype in (np.int8, np.uint8)
             x64 = (not packed) and X.dtype == np.float64
             force_fp32 = os.environ.get("PYGEMMA_ROTATE", "") == "fp32" and not (packed or x8 or x64)
             esz = 1 if x8 else (8 if x64 else 4)
-            pb_max, ldX = _batch_geometry(n, a, b)
+            pb_max, ldX = _batch_geometry(n, a, b, gxe)
             bpr = (n + 3) // 4
             direct = (not packed) and _lib.is_pinned(X)        # X itself is page-locked: DMA straight out of it
             snp_major = (not packed) and X.flags.f_contiguous and not X.flags.c_contiguous     # (float32 only: pygemma() sees to it)
@@ -403,30 +423,41 @@ def _run_block(job, device, a, b, dU, comm):
                     else:            # the column window [s, e) of every sample row, at row pitch ldX
                         _put_window(ctx, X, s, e, w.X.ptr, ldX * esz, w.inp)
                 t_dma = time.time()
+
                 # ---- rotation: decode + impute + rotate for .bed records; otherwise the path is chosen on the device
-                if packed:
-                    _lib.check(L.pg_rotate_bed_dev(ctx.handle, n, pb, dprep.ptr, w.X.ptr, bpr, int(X.count_A1), w.Xr.ptr, ldx,
-                                                   w.work.ptr), "pg_rotate_bed_dev")
-                elif x64:
-                    is_geno = C.c_int(0)
-                    _lib.check(L.pg_rotate_geno_f64_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, ldX, w.Xr.ptr, ldx, w.work.ptr,
-                                                        C.byref(is_geno)), "pg_rotate_geno_f64_dev")
-                    if not is_geno.value:
-                        w.Xf = w.Xf or ctx.alloc(n * ldX * 4)      # float32 image of a block that does not qualify for the genotype path
-                        _lib.check(L.pg_cast_f64_f32_dev(ctx.handle, n, pb, dXc.ptr, ldX, w.Xf.ptr, ldX), "pg_cast_f64_f32_dev")
-                        _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, w.Xf.ptr, ldX, w.Xr.ptr, ldx), "pg_rotate_dev")
-                elif x8:         # 8-bit block (always finite): genotype codes or split planes, chosen on the device
-                    _lib.check(L.pg_rotate_auto_i8_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, int(X.dtype == np.uint8), ldX,
-                                                       w.Xr.ptr, ldx, w.work.ptr, None), "pg_rotate_auto_i8_dev")
-                elif eigen and force_fp32:   # PYGEMMA_ROTATE=fp32: the reference-arithmetic kernel for every block (tests, A/B)
-                    _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, dXc.ptr, ldX, w.Xr.ptr, ldx), "pg_rotate_dev")
-                elif eigen:      # float32 block: path (genotype fp16x2 / split planes / fp32 MFMA) chosen on the device, no host wait
-                    _lib.check(L.pg_rotate_auto_dev(ctx.handle, n, pb, dU.ptr, n, dprep.ptr, dXc.ptr, ldX, w.Xr.ptr, ldx,
-                                                    w.work.ptr, None), "pg_rotate_auto_dev")
-                elif not snp_major:
-                    _lib.check(L.pg_transpose_dev(ctx.handle, n, pb, dXc.ptr, ldX, w.Xr.ptr, ldx), "pg_transpose_dev")
+                xf = []          # float64 block off the genotype path: its float32 image in w.Xf, cast once for both rotations
+
+                def rotate(dU, dprep, dXr):
+                    if packed:
+                        _lib.check(L.pg_rotate_bed_dev(ctx.handle, n, pb, dprep.ptr, w.X.ptr, bpr, int(X.count_A1), dXr, ldx,
+                                                       w.work.ptr), "pg_rotate_bed_dev")
+                    elif x64:
+                        if not xf:       # the genotype check depends on X only: a block that failed it for U fails it for Ue
+                            is_geno = C.c_int(0)
+                            _lib.check(L.pg_rotate_geno_f64_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, ldX, dXr, ldx, w.work.ptr,
+                                                                C.byref(is_geno)), "pg_rotate_geno_f64_dev")
+                            if is_geno.value:
+                                return
+                            w.Xf = w.Xf or ctx.alloc(n * ldX * 4)      # float32 image of a block that does not qualify for the genotype path
+                            _lib.check(L.pg_cast_f64_f32_dev(ctx.handle, n, pb, dXc.ptr, ldX, w.Xf.ptr, ldX), "pg_cast_f64_f32_dev")
+                            xf.append(True)
+                        _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, w.Xf.ptr, ldX, dXr, ldx), "pg_rotate_dev")
+                    elif x8:         # 8-bit block (always finite): genotype codes or split planes, chosen on the device
+                        _lib.check(L.pg_rotate_auto_i8_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, int(X.dtype == np.uint8), ldX,
+                                                           dXr, ldx, w.work.ptr, None), "pg_rotate_auto_i8_dev")
+                    elif eigen and force_fp32:   # PYGEMMA_ROTATE=fp32: the reference-arithmetic kernel for every block (tests, A/B)
+                        _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, dXc.ptr, ldX, dXr, ldx), "pg_rotate_dev")
+                    elif eigen:      # float32 block: path (genotype fp16x2 / split planes / fp32 MFMA) chosen on the device, no host wait
+                        _lib.check(L.pg_rotate_auto_dev(ctx.handle, n, pb, dU.ptr, n, dprep.ptr, dXc.ptr, ldX, dXr, ldx,
+                                                        w.work.ptr, None), "pg_rotate_auto_dev")
+                    elif not snp_major:
+                        _lib.check(L.pg_transpose_dev(ctx.handle, n, pb, dXc.ptr, ldX, dXr, ldx), "pg_transpose_dev")
+
+                rotate(dU, dprep, w.Xr.ptr)
+                if gxe:          # x o e: the same path on the same raw block, with Ue in U's place
+                    rotate(dUe, dprepe, w.XEr.ptr)
                 # ---- the mode's kernels, and the result rows back
-                job.mode.launch(ctx, dev, pb, w.Xr.ptr, w.res.ptr)
+                job.mode.launch(ctx, dev, pb, w.Xr.ptr, w.res.ptr, *((w.XEr.ptr,) if gxe else ()))
                 _lib.check(L.pg_memcpy_d2h_async(ctx.handle, w.out, w.res.ptr, pb * nout), "pg_memcpy_d2h_async")
                 ctx.sync()
                 return t_dma, prefetched     # (a prefetched buffer is freed with the prefetcher: hipFree would drain the device here)
@@ -441,11 +472,11 @@ def _run_block(job, device, a, b, dU, comm):
                         # one device allocation per worker, cut into its buffers: every hipMalloc / hipFree of a few hundred MB costs
                         # 1 - 2 ms of host time that nothing overlaps (r4: worker set-up 3.8 ms, teardown 9.2 ms with five allocations)
                         sizes = [raw_bytes, pb_max * n * 4 if (snp_major and eigen) else 0, pb_max * ldx * 4, pb_max * nout,
-                                 L.pg_geno_work_bytes(n, pb_max) if eigen else 0]
+                                 L.pg_geno_work_bytes(n, pb_max) if eigen else 0, pb_max * ldx * 4 if gxe else 0]
                         offs = np.concatenate([[0], np.cumsum([(int(z) + 255) // 256 * 256 for z in sizes])])
                         arena = ctx.alloc(int(offs[-1]))
                         w = SimpleNamespace(**{k: _View(arena.ptr + int(o)) if z else None
-                                               for k, o, z in zip(("X", "T", "Xr", "res", "work"), offs[:-1], sizes)}, Xf=None)
+                                               for k, o, z in zip(("X", "T", "Xr", "res", "work", "XEr"), offs[:-1], sizes)}, Xf=None)
                         stg = _Pinned(ctx, pb_max * nout) if direct else _Pinned(ctx, raw_bytes, pb_max * nout)
                         w.inp, w.out = (None, *stg.bufs) if direct else stg.bufs
                         hres = (C.c_char * (pb_max * nout)).from_address(w.out)
@@ -766,6 +797,67 @@ def pygemma_score(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True,
     return results_df
 
 
+def _e_in_span(W, e):
+    """True when the float32 column e lies in the span of W's columns, up to float32 rounding: the least-squares residual of e on W
+    (fp64) is within a few float32 ulps of e's own terms.  Scale-invariant: an uncentred e beside an intercept (a blood pressure
+    of 130 +- 15, a birth year) has a residual of its spread's size and is accepted at any n."""
+    W64, e64 = W.astype(np.float64), e.astype(np.float64)
+    coef = np.linalg.lstsq(W64, e64, rcond=None)[0]
+    r = e64 - W64 @ coef
+    scale = np.linalg.norm(e64) + np.abs(coef) @ np.linalg.norm(W64, axis=0)
+    return bool(np.linalg.norm(r) <= 16 * np.finfo(np.float32).eps * scale)
+
+
+def pygemma_gxe(Y, X, W, K, E, Z=None, snps=None, verbose=0, disable_checks=True, eigen=True, nproc=1, eigenpairs=None, checkpoint=None,
+                stats=None):
+    """SNP-by-environment interaction scan (GEMMA's -gxe): per SNP j, the REML Wald test of beta_gxe in
+
+        y = W alpha + e gamma + x_j beta_x + (x_j o e) beta_gxe + g + eps,   g ~ N(0, lambda/tau K),  eps ~ N(0, 1/tau I)
+
+    with lambda searched per SNP under this full model (lmm.pygemma's decade scan + brentq + Newton; no grid).  E: the environment
+    e, (n,) or (n, 1), cast to float32 like W; it always enters the model as a covariate (appended to W).  Same inputs otherwise as
+    lmm.pygemma (Y, X, W, K, Z, snps, eigen=True, nproc, eigenpairs, checkpoint, stats; every X kind it takes).  Returns the columns
+    beta, se_beta, tau, lambda, F_wald, p_wald[, SNPs] of lmm.pygemma, with beta = beta_gxe and p_wald from F(1, n - c - 3).
+
+    In the eigenbasis row j is calculate(d, U'y, [U'W, U'e, U'x_j], U'(x_j o e)).  U'(x o e) = (diag(e) U)' x: each GPU scales
+    its copy of U once and rotates every SNP batch twice, by the path lmm.pygemma picks for X (which depends on X only).  A
+    missing .bed call is imputed before e is applied, as in host X o e.  On the int8 x 3 genotype path diag(e) U is held per
+    eigenvector in fixed point relative to max_i |e_i u_ik|: an eigenvector whose weight e concentrates on few samples loses
+    relative precision elsewhere, the error class of localised eigenvectors on that path.  Degenerate SNPs (constant, x o e
+    in span([W, e, x]), non-finite) give NaN where calculate() does.  Refused before any device work: E not (n,) / (n, 1) or not
+    finite, e in span(W) (rank of [W, e] in fp64), W with other than 1..28 columns, n - c - 3 <= 0, eigen=False (x o e cannot be
+    formed from rotated X: use ops.gxe with U'X and U'(X o e)).  The checkpoint manifest records the interaction run (`gxe`,
+    `e_crc`), so a Wald run's directory is refused and vice versa."""
+    if not eigen:
+        raise ValueError("pygemma_gxe needs eigen=True: x o e cannot be formed from rotated genotypes; in the eigenbasis call "
+                         "ops.gxe(d, [U'W, U'e], U'y, U'X, U'(X o e)) instead")
+    W = np.asarray(W)
+    if W.ndim != 2 or not 1 <= W.shape[1] <= 28:
+        raise ValueError(f"the interaction scan takes W with 1 to 28 columns (e makes one more covariate), got W {W.shape}")
+    n = X.shape[0]
+    e = np.asarray(E)
+    if e.shape not in ((n,), (n, 1)):
+        raise ValueError(f"E must be of shape ({n},) or ({n}, 1), got {e.shape}")
+    e = e.reshape(-1).astype(np.float32)
+    if not np.isfinite(e).all():
+        raise ValueError("E holds non-finite values")
+    if W.shape[0] != n:
+        raise ValueError(f"shape mismatch: X has {n} rows, W {W.shape[0]}")
+    W32 = W.astype(np.float32)
+    We = np.concatenate([W32, e[:, None]], axis=1)
+    if _e_in_span(W32, e):
+        raise ValueError("[W, e] is rank-deficient: e lies in the span of W's columns")
+    c = We.shape[1]
+    if n - c - 2 <= 0:
+        raise ValueError(f"the interaction scan needs n - c - 3 > 0 (n = {n}, c = {c - 1} columns of W)")
+    out = _scan(Y, X, We, K, Z=Z, verbose=verbose, disable_checks=disable_checks, eigen=True, nproc=nproc, eigenpairs=eigenpairs,
+                checkpoint=checkpoint, stats=stats, gxe=e)
+    results_df = pd.DataFrame(out, columns=list(out))
+    if snps is not None:
+        results_df["SNPs"] = snps
+    return results_df
+
+
 def _null_lambda(L, n, c, d, Wr, yr):
     """lambda0 of the score test: the ML lambda of y ~ W on GPU 0 (pg_score_null_dev), read back as one float32."""
     with _lib.Context(0) as ctx:
@@ -893,10 +985,10 @@ def _check_manifest(checkpoint, key):
 
 
 def _scan(Y, X, W, K, *, Z=None, verbose=0, disable_checks=True, grid=False, eigen=True, nproc=1, checkpoint=None, lrt=False,
-          eigenpairs=None, stats=None, npheno=0, score=False):
-    """The pipeline under pygemma (npheno = 0: Y is one phenotype), pygemma_multi (Y: float32 (n, npheno)) and pygemma_score
-    (score = True: F_wald / p_wald hold F_score / p_score).  Returns the result columns: arrays of p values, or npheno x p with
-    npheno > 0."""
+          eigenpairs=None, stats=None, npheno=0, score=False, gxe=None):
+    """The pipeline under pygemma (npheno = 0: Y is one phenotype), pygemma_multi (Y: float32 (n, npheno)), pygemma_score
+    (score = True: F_wald / p_wald hold F_score / p_score) and pygemma_gxe (gxe: the float32 environment (n,), already the last
+    column of W).  Returns the result columns: arrays of p values, or npheno x p with npheno > 0."""
     L = _lib.load()
     Y, X, W, K = _inputs(L, Y, X, W, K, Z, eigen, eigenpairs, score)
     packed = isinstance(X, PackedBed)
@@ -923,7 +1015,7 @@ def _scan(Y, X, W, K, *, Z=None, verbose=0, disable_checks=True, grid=False, eig
             # the eigensolver leaves PCIe idle for ~0.6 s at n = 10 000 (52 s at 50 000): X starts moving now
             try:
                 if _lib.is_pinned(X):
-                    pre = _Prefetch(L, X, blocks, n, X.dtype.itemsize, verbose)
+                    pre = _Prefetch(L, X, blocks, n, X.dtype.itemsize, verbose, gxe is not None)
             except _lib.PgError as ex:
                 _log(verbose, f"prefetch not started ({ex})")
         if eigen and not packed and X.size and not _lib.is_pinned(X) and (X.flags.c_contiguous or X.flags.f_contiguous) and X.nbytes >= (256 << 20):
@@ -973,10 +1065,13 @@ def _scan(Y, X, W, K, *, Z=None, verbose=0, disable_checks=True, grid=False, eig
         if checkpoint:
             # identity of the run: shapes, options, batch geometry and the SNP-independent inputs themselves (rotated y, W and the
             # eigenvalues, byte for byte); the genotypes are fingerprinted per part (_block_fingerprint)
-            _check_manifest(checkpoint, {
+            key = {
                 "n": int(n), "p": int(p), "c": int(c), "grid": bool(grid), "eigen": bool(eigen), "ndev": int(ndev), "lrt": bool(lrt),
                 "batch_snps": int(_BATCH_SNPS), "batch_bytes": int(_BATCH_BYTES), "batch_min": int(_BATCH_MIN), "batch_count": int(_BATCH_COUNT),
-                "y_crc": _crc(yr1), "w_crc": _crc(Wr), "d_crc": _crc(eigenVals)})
+                "y_crc": _crc(yr1), "w_crc": _crc(Wr), "d_crc": _crc(eigenVals)}
+            if gxe is not None:        # an interaction run: never mixed with a Wald run's parts (whose manifest has no such keys)
+                key.update({"gxe": True, "e_crc": _crc(gxe)})
+            _check_manifest(checkpoint, key)
         t2 = time.time()
         if pre is not None:
             pre.join()
@@ -1003,8 +1098,8 @@ def _scan(Y, X, W, K, *, Z=None, verbose=0, disable_checks=True, grid=False, eig
             comms = _make_comms(L, ndev)      # RCCL communicator over the GPUs of this process: U goes GPU 0 -> all over xGMI
             for g in range(1, ndev):          # receive buffers made here: an allocation failure surfaces before any thread waits in the collective
                 dUs[g] = comms[g].ctx.alloc(n * n * 4)
-        job = _Job(n, c, eigenVals, Wr, yr1, X, grid, eigen, _scan_mode(L, n, c, grid, lrt, npheno, lam0), checkpoint, stats, pre,
-                   verbose, out, errs)
+        job = _Job(n, c, eigenVals, Wr, yr1, X, grid, eigen, _scan_mode(L, n, c, grid, lrt, npheno, lam0, gxe is not None), checkpoint,
+                   stats, pre, verbose, out, errs, gxe)
         threads = [threading.Thread(target=_run_block, args=(job, g, a, b, dUs[g], comms[g] if comms else None))
                    for g, (a, b) in enumerate(blocks)]
         for th in threads:

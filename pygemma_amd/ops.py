@@ -78,6 +78,47 @@ def score(d, Wr, yr, Xr, lam0=None, ctx=None):
             ctx.close()
 
 
+def gxe(d, Wr, yr, Xr, XEr, ctx=None, want_p=True, return_stats=False):
+    """The SNP-by-environment Wald test (pg_assoc_gxe_dev) on the GPU: per SNP j, the REML Wald test of XEr[:, j] in
+    y ~ Wr + Xr[:, j] + XEr[:, j], i.e. calculate(d, yr, [Wr, Xr[:, j]], XEr[:, j]) with lambda searched per SNP.
+    d (n,), Wr (n,c) with U'e as its last column, yr (n,) or (n,1), Xr = U'X and XEr = U'(X o e), each (n,p) in the REFERENCE
+    layout, all in the eigenbasis.  Returns dict(beta, se_beta, tau, lambda, F_wald, p_wald[, n_evals]); beta is beta_gxe and
+    p_wald uses F(1, n - c - 2)."""
+    L = _lib.load()
+    own = ctx is None
+    ctx = ctx or _lib.Context(0)
+    try:
+        d, Wr, yr, Xr, XEr = _f32(d), _f32(Wr), _f32(np.asarray(yr).reshape(-1)), _f32(Xr), _f32(XEr)
+        n, c = Wr.shape
+        p = Xr.shape[1]
+        assert d.shape == (n,) and yr.shape == (n,) and Xr.shape == (n, p) and XEr.shape == (n, p)
+        dd, dW, dy = ctx.to_device(d), ctx.to_device(Wr), ctx.to_device(yr)
+        dX, dXE = ctx.to_device(Xr), ctx.to_device(XEr)
+        dXr, dXEr = ctx.alloc(max(p, 1) * n * 4), ctx.alloc(max(p, 1) * n * 4)
+        out = [ctx.alloc(max(p, 1) * 4) for _ in range(4)] + [ctx.alloc(max(p, 1) * 8) for _ in range(2)]
+        dst = ctx.alloc(16)
+        _lib.check(L.pg_memset(ctx.handle, dst.ptr, 0, 16), "pg_memset")
+        if p:
+            _lib.check(L.pg_transpose_dev(ctx.handle, n, p, dX.ptr, p, dXr.ptr, n), "pg_transpose_dev")
+            _lib.check(L.pg_transpose_dev(ctx.handle, n, p, dXE.ptr, p, dXEr.ptr, n), "pg_transpose_dev")
+        _lib.check(L.pg_assoc_gxe_dev(ctx.handle, n, c, p, dd.ptr, dW.ptr, dy.ptr, dXr.ptr, n, dXEr.ptr, n,
+                                      *[b.ptr for b in out[:5]], out[5].ptr if want_p else None, dst.ptr), "pg_assoc_gxe_dev")
+        ctx.sync()
+        res = {col: b.download((p,), np.float32 if k < 4 else np.float64)
+               for k, (col, b) in enumerate(zip(("beta", "se_beta", "tau", "lambda", "F_wald", "p_wald"), out))}
+        res["lambda"] = res["lambda"].astype(np.float64)
+        if not want_p:
+            res["p_wald"] = None
+        if return_stats:
+            res["n_evals"] = dst.download((2,), np.uint64).astype(np.int64)
+        for b in (dd, dW, dy, dX, dXE, dXr, dXEr, dst, *out):
+            b.free()
+        return res
+    finally:
+        if own:
+            ctx.close()
+
+
 def fdist_sf(F, dfd, ctx=None):
     L = _lib.load()
     own = ctx is None
