@@ -3,8 +3,10 @@
 The MI355X path has NO CPU fallback: if the shared library is missing or no GPU is visible the
 calls raise.  The checker (the CPU oracle) is test infrastructure and is never imported from here.
 """
+import contextlib
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -12,167 +14,64 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYGEMMA_HIP_LIB") or os.path.join(_HERE, "lib", "libpygemma_hip.so")   # env: A/B builds
 _lib = None
 
-SYMBOLS = [
-    "pg_last_error", "pg_version", "pg_device_count", "pg_ctx_create", "pg_ctx_create_on_stream",
-    "pg_ctx_destroy", "pg_ctx_sync", "pg_ctx_device", "pg_mem_info", "pg_malloc", "pg_free", "pg_memcpy_h2d", "pg_memcpy_d2h",
-    "pg_memset", "pg_memcpy2d_h2d", "pg_event_create", "pg_event_destroy", "pg_event_record", "pg_event_elapsed_ms",
-    "pg_kinship_dev", "pg_geno_prep_bytes", "pg_geno_work_bytes", "pg_geno_prep_dev", "pg_rotate_geno_dev", "pg_assoc_dev", "pg_assoc", "pg_fdist_sf_dev", "pg_transpose_dev", "pg_rotate_dev", "pg_syevd_dev",
-    "pg_precompute_mat_dev", "pg_newton_dev", "pg_reml_scalars_dev", "pg_ml_scalars_dev", "pg_rotate_bed_dev", "pg_rotate_geno_i8_dev", "pg_cast_i8_f32_dev", "pg_assoc_multi", "pg_rotate_geno_f64_dev", "pg_cast_f64_f32_dev",
-    "pg_host_alloc", "pg_host_free", "pg_host_register", "pg_host_unregister", "pg_memcpy_h2d_async", "pg_memcpy_d2h_async",
-    "pg_memcpy_d2d_async", "pg_memcpy2d_h2d_async", "pg_stage_rows", "pg_event_sync", "pg_stream_wait_event",
-    "pg_comm_unique_id", "pg_comm_init_rank", "pg_comm_init_all", "pg_comm_destroy", "pg_comm_size", "pg_comm_rank",
-    "pg_comm_broadcast_dev", "pg_comm_allgather_dev", "pg_comm_allreduce_f64_dev", "pg_comm_barrier", "pg_comm_group_start",
-    "pg_comm_group_end", "pgx_dgemm_dev", "pgx_sytrd_dev", "pgx_stedc_dev", "pgx_sb2_stage1_dev", "pgx_sb2_stage2_dev", "pgx_sb2_set_debug", "pg_kinship_geno_dev", "pg_assoc_lrt_dev", "pg_rotate_auto_dev", "pg_assoc_set_eval_trace", "pg_assoc_warm", "pg_rotate_auto_i8_dev",
-    "pg_zkzt_dev", "pgx_dgemm_ex_dev", "pgx_ring_stamps", "pg_assoc_pheno_dev", "pg_assoc_pheno_warm", "pg_score_null_dev", "pg_score_dev",
-    "pg_kinship_acc_bytes", "pg_kinship_bed_acc_dev", "pg_kinship_x_acc_dev", "pg_kinship_finish_dev",
-    "pg_assoc_gxe_dev", "pg_assoc_gxe_warm", "pg_gxe_scale_u_dev",
-]
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "pygemma_hip.h")
+SYMBOLS = []     # the functions HEADER declares, in its order: filled by load()
+_CTYPES = {"int": C.c_int, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
 
 
 class PgError(RuntimeError):
     pass
 
 
+def _ctype(decl, fn, ret=False):
+    """ctypes type of one parameter ('const float *Xr', 'int64_t n') or return type ('const char *', 'void') of function fn.
+    Every pointer is a c_void_p: it takes byref(), ctypes arrays, ndarray.ctypes pointers, ints, c_void_p and None."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        return C.c_char_p if ret and words == ["char", "*"] else C.c_void_p
+    if not ret and len(words) > 1:
+        words = words[:-1]                   # the parameter's name
+    ctype = " ".join(words)
+    if ret and ctype == "void":
+        return None
+    if ctype not in _CTYPES:                 # never ctypes' default int: it would truncate whatever this is
+        raise PgError(f"{fn}: C type '{ctype}' of '{decl.strip()}' has no ctypes mapping (pygemma_amd/_lib.py)")
+    return _CTYPES[ctype]
+
+
+def parse_header(text):
+    """[(name, restype, argtypes)] of the pg_* / pgx_* functions a C header declares, in its order.  The header is plain C
+    (include/pygemma_hip.h): comments and preprocessor lines go, typedefs and the enum hold no call, 'ret name(params);' is left."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r'^\s*#.*$|extern\s+"C"\s*\{', "", text, flags=re.M)
+    out = []
+    for stmt in text.split(";"):
+        m = re.fullmatch(r"(.*?)\b(pgx?_\w+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        if m:
+            ret, fn, params = m.groups()
+            args = [] if params.strip() == "void" else [_ctype(a, fn) for a in params.split(",")]
+            out.append((fn, _ctype(ret, fn, ret=True), args))
+    return out
+
+
 def load():
-    """Load the HIP library (build it first with __graft_entry__.build() / make -C pygemma_amd/csrc)."""
+    """Load the HIP library (build it first with __graft_entry__.build() / make -C pygemma_amd/csrc) and give every function
+    the signature include/pygemma_hip.h declares: the header is the one place an entry point is registered."""
     global _lib
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
         raise PgError(f"{LIB_PATH} not found: build the HIP extension (python -c 'import __graft_entry__ as g; g.build()'). "
                       "pygemma_amd has no CPU fallback.")
+    if not os.path.exists(HEADER):
+        raise PgError(f"{HEADER} not found: the signatures of {LIB_PATH} are read from it")
     L = C.CDLL(LIB_PATH)
-    vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
-    L.pg_last_error.restype = C.c_char_p
-    L.pg_version.restype = C.c_char_p
-    L.pg_device_count.restype = i32
-    L.pg_ctx_create.argtypes = [i32, C.POINTER(vp)]
-    L.pg_ctx_create_on_stream.argtypes = [i32, vp, C.POINTER(vp)]
-    L.pg_ctx_destroy.argtypes = [vp]
-    L.pg_ctx_destroy.restype = None
-    L.pg_ctx_sync.argtypes = [vp]
-    L.pg_ctx_device.argtypes = [vp]
-    L.pg_mem_info.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.pg_malloc.argtypes = [vp, sz, C.POINTER(vp)]
-    L.pg_free.argtypes = [vp, vp]
-    L.pg_memcpy_h2d.argtypes = [vp, vp, vp, sz]
-    L.pg_memcpy_d2h.argtypes = [vp, vp, vp, sz]
-    L.pg_memset.argtypes = [vp, vp, i32, sz]
-    L.pg_assoc_dev.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.pg_assoc.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.pg_assoc_lrt_dev.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp, i64, i32] + [vp] * 10
-    L.pg_assoc_lrt_dev.restype = i32
-    L.pg_fdist_sf_dev.argtypes = [vp, i64, vp, C.c_double, vp]
-    L.pg_assoc_multi.argtypes = [i32, i64, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
-    L.pg_assoc_multi.restype = i32
-    L.pg_transpose_dev.argtypes = [vp, i64, i64, vp, i64, vp, i64]
-    L.pg_rotate_dev.argtypes = [vp, i64, i64, vp, i64, vp, i64, vp, i64]
-    L.pg_kinship_dev.argtypes = [vp, i64, i64, vp, i64, vp]
-    L.pg_kinship_geno_dev.argtypes = [vp, i64, i64, vp, i64, i32, vp]
-    L.pg_kinship_geno_dev.restype = i32
-    L.pg_kinship_acc_bytes.argtypes = [i64, i64]
-    L.pg_kinship_acc_bytes.restype = sz
-    L.pg_kinship_bed_acc_dev.argtypes = [vp, i64, i64, vp, i64, i32, i32, vp]
-    L.pg_kinship_bed_acc_dev.restype = i32
-    L.pg_kinship_x_acc_dev.argtypes = [vp, i64, i64, vp, i32, i64, i32, i32, vp]
-    L.pg_kinship_x_acc_dev.restype = i32
-    L.pg_kinship_finish_dev.argtypes = [vp, i64, i64, vp, vp]
-    L.pg_kinship_finish_dev.restype = i32
-    L.pg_geno_prep_bytes.argtypes = [i64]
-    L.pg_geno_prep_bytes.restype = sz
-    L.pg_geno_work_bytes.argtypes = [i64, i64]
-    L.pg_geno_work_bytes.restype = sz
-    L.pg_geno_prep_dev.argtypes = [vp, i64, vp, i64, vp]
-    L.pg_geno_prep_dev.restype = i32
-    L.pg_rotate_geno_dev.argtypes = [vp, i64, i64, vp, vp, i64, vp, i64, vp, C.POINTER(i32)]
-    L.pg_rotate_geno_dev.restype = i32
-    L.pg_assoc_set_eval_trace.argtypes = [vp, vp]
-    L.pg_assoc_set_eval_trace.restype = i32
-    L.pg_assoc_warm.argtypes = [vp, i64, i32]
-    L.pg_assoc_warm.restype = i32
-    L.pg_assoc_pheno_dev.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.pg_assoc_pheno_dev.restype = i32
-    L.pg_assoc_pheno_warm.argtypes = [vp, i64, i32, i32, i64]
-    L.pg_assoc_pheno_warm.restype = i32
-    L.pg_score_null_dev.argtypes = [vp, i64, i32, vp, vp, vp, vp]
-    L.pg_score_null_dev.restype = i32
-    L.pg_score_dev.argtypes = [vp, i64, i32, i64, vp, vp, vp, C.c_float, vp, i64, vp, vp, vp, vp, vp, vp]
-    L.pg_score_dev.restype = i32
-    L.pg_assoc_gxe_dev.argtypes = [vp, i64, i32, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.pg_assoc_gxe_dev.restype = i32
-    L.pg_assoc_gxe_warm.argtypes = [vp, i64, i32]
-    L.pg_assoc_gxe_warm.restype = i32
-    L.pg_gxe_scale_u_dev.argtypes = [vp, i64, vp, i64, vp, vp]
-    L.pg_gxe_scale_u_dev.restype = i32
-    L.pg_rotate_auto_i8_dev.argtypes = [vp, i64, i64, vp, vp, i32, i64, vp, i64, vp, vp]
-    L.pg_rotate_auto_i8_dev.restype = i32
-    L.pg_rotate_auto_dev.argtypes = [vp, i64, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp]
-    L.pg_rotate_auto_dev.restype = i32
-    L.pg_rotate_bed_dev.argtypes = [vp, i64, i64, vp, vp, i64, i32, vp, i64, vp]
-    L.pg_rotate_bed_dev.restype = i32
-    L.pg_rotate_geno_i8_dev.argtypes = [vp, i64, i64, vp, vp, i32, i64, vp, i64, vp, C.POINTER(i32)]
-    L.pg_rotate_geno_i8_dev.restype = i32
-    L.pg_cast_i8_f32_dev.argtypes = [vp, i64, i64, vp, i32, i64, vp, i64]
-    L.pg_cast_i8_f32_dev.restype = i32
-    L.pg_rotate_geno_f64_dev.argtypes = [vp, i64, i64, vp, vp, i64, vp, i64, vp, C.POINTER(i32)]
-    L.pg_rotate_geno_f64_dev.restype = i32
-    L.pg_cast_f64_f32_dev.argtypes = [vp, i64, i64, vp, i64, vp, i64]
-    L.pg_cast_f64_f32_dev.restype = i32
-    L.pg_memcpy2d_h2d.argtypes = [vp, vp, sz, vp, sz, sz, sz]
-    L.pg_event_create.argtypes = [vp, C.POINTER(vp)]
-    L.pg_event_destroy.argtypes = [vp, vp]
-    L.pg_event_record.argtypes = [vp, vp]
-    L.pg_event_elapsed_ms.argtypes = [vp, vp, vp, C.POINTER(C.c_float)]
-    L.pg_syevd_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    f32 = C.c_float
-    L.pg_precompute_mat_dev.argtypes = [vp, i64, i32, f32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
-    L.pg_newton_dev.argtypes = [vp, i64, i32, f32, f32, f32, vp, vp, vp, vp]
-    L.pg_reml_scalars_dev.argtypes = [vp, i64, i32, vp, vp]
-    L.pg_ml_scalars_dev.argtypes = [vp, i64, vp, vp]
-    L.pg_ml_scalars_dev.restype = i32
-    L.pg_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
-    L.pg_host_free.argtypes = [vp, vp]
-    L.pg_host_register.argtypes = [vp, vp, sz]
-    L.pg_host_unregister.argtypes = [vp, vp]
-    L.pg_memcpy_h2d_async.argtypes = [vp, vp, vp, sz]
-    L.pg_memcpy_d2h_async.argtypes = [vp, vp, vp, sz]
-    L.pg_memcpy_d2d_async.argtypes = [vp, vp, vp, sz]
-    L.pg_memcpy2d_h2d_async.argtypes = [vp, vp, sz, vp, sz, sz, sz]
-    L.pg_stage_rows.argtypes = [vp, sz, vp, sz, sz, sz, i32]
-    L.pg_event_sync.argtypes = [vp, vp]
-    L.pg_stream_wait_event.argtypes = [vp, vp]
-    L.pg_comm_unique_id.argtypes = [vp]
-    L.pg_comm_init_rank.argtypes = [vp, i32, i32, vp, C.POINTER(vp)]
-    L.pg_comm_init_all.argtypes = [i32, C.POINTER(vp), C.POINTER(vp)]
-    L.pg_comm_destroy.argtypes = [vp]
-    L.pg_comm_size.argtypes = [vp]
-    L.pg_comm_rank.argtypes = [vp]
-    L.pg_comm_broadcast_dev.argtypes = [vp, vp, sz, i32]
-    L.pg_comm_allgather_dev.argtypes = [vp, vp, vp, sz]
-    L.pg_comm_allreduce_f64_dev.argtypes = [vp, vp, sz, i32]
-    L.pg_comm_barrier.argtypes = [vp]
-    L.pgx_dgemm_dev.argtypes = [vp, i32, i64, i64, i64, C.c_double, vp, i64, vp, i64, C.c_double, vp, i64]
-    L.pgx_dgemm_ex_dev.argtypes = [vp, i32, i32, i64, i64, i64, C.c_double, vp, i64, vp, i64, C.c_double, vp, i64]
-    L.pgx_dgemm_ex_dev.restype = i32
-    L.pg_zkzt_dev.argtypes = [vp, i64, i64, vp, i32, i64, vp, i32, i64, vp, i64]
-    L.pg_zkzt_dev.restype = i32
-    L.pgx_sytrd_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.pgx_stedc_dev.argtypes = [vp, i64, vp, vp, vp, vp]
-    L.pgx_sb2_stage1_dev.argtypes = [vp, i64, vp, vp, vp, vp]
-    L.pgx_sb2_stage2_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.pgx_sb2_set_debug.argtypes = [vp]
-    for name in ("pg_host_alloc", "pg_host_free", "pg_host_register", "pg_host_unregister", "pg_memcpy_h2d_async", "pg_memcpy_d2h_async",
-                 "pg_memcpy_d2d_async", "pg_memcpy2d_h2d_async", "pg_stage_rows", "pg_event_sync", "pg_stream_wait_event", "pg_comm_unique_id",
-                 "pg_comm_init_rank", "pg_comm_init_all", "pg_comm_destroy", "pg_comm_size", "pg_comm_rank", "pg_comm_broadcast_dev",
-                 "pg_comm_allgather_dev", "pg_comm_allreduce_f64_dev", "pg_comm_barrier", "pg_comm_group_start", "pg_comm_group_end",
-                 "pgx_dgemm_dev", "pgx_sytrd_dev", "pgx_stedc_dev", "pgx_sb2_stage1_dev", "pgx_sb2_stage2_dev", "pgx_sb2_set_debug"):
-        getattr(L, name).restype = i32
-    for name in ("pg_ctx_create", "pg_ctx_create_on_stream", "pg_ctx_sync", "pg_ctx_device", "pg_malloc", "pg_free",
-                 "pg_memcpy_h2d", "pg_memcpy_d2h", "pg_memset", "pg_assoc_dev", "pg_assoc", "pg_fdist_sf_dev",
-                 "pg_transpose_dev", "pg_rotate_dev", "pg_syevd_dev", "pg_memcpy2d_h2d", "pg_event_create", "pg_event_destroy",
-                 "pg_event_record", "pg_event_elapsed_ms", "pg_kinship_dev", "pg_precompute_mat_dev", "pg_newton_dev",
-                 "pg_reml_scalars_dev"):
-        getattr(L, name).restype = i32
+    with open(HEADER) as hdr:
+        decls = parse_header(hdr.read())
+    for fn, restype, argtypes in decls:
+        f = getattr(L, fn)
+        f.restype, f.argtypes = restype, argtypes
+    SYMBOLS[:] = [fn for fn, _, _ in decls]
     _lib = L
     return L
 
@@ -195,6 +94,8 @@ class DeviceBuffer:
         if self.ptr:
             load().pg_free(self.ctx.handle, self.ptr)
             self.ptr = None
+        if self in self.ctx._bufs:
+            self.ctx._bufs.remove(self)
 
     def upload(self, arr):
         arr = np.ascontiguousarray(arr)
@@ -242,9 +143,8 @@ class Context:
 
     def close(self):
         if self.handle:
-            for b in self._bufs:
+            for b in list(self._bufs):
                 b.free()
-            self._bufs = []
             load().pg_ctx_destroy(self.handle)
             self.handle = None
 
@@ -259,6 +159,25 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+@contextlib.contextmanager
+def scope(ctx=None, device=0):
+    """The context and device buffers of one wrapper call: yields ctx, or a Context(device) of its own that is closed on exit.
+    On exit from a borrowed ctx every DeviceBuffer allocated on it since entry is freed (hipFree waits for the device, so after
+    the wrapper's downloads) and leaves ctx._bufs, whether the body returned or raised; what the caller had allocated stays.
+    Scopes on one context nest (model._ml_scalars around precompute_mat).  A Context is used by one thread at a time — lmm.py
+    gives every worker thread its own — so every buffer that appears between entry and exit is this scope's."""
+    if ctx is None:
+        with Context(device) as own:
+            yield own
+        return
+    before = set(ctx._bufs)
+    try:
+        yield ctx
+    finally:
+        for b in [b for b in ctx._bufs if b not in before]:
+            b.free()
 
 
 def device_count():

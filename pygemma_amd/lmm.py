@@ -84,13 +84,12 @@ def _rotate_small(ctx, L, n, dU, A):
     """U.T @ A for a narrow host matrix A (n,q) (Y and W): same MFMA kernel, SNP-major result transposed back."""
     q = A.shape[1]
     ldx = (n + 63) // 64 * 64
-    dA = ctx.to_device(np.ascontiguousarray(A, np.float32))
-    dO = ctx.alloc(q * ldx * 4)
-    _lib.check(L.pg_rotate_dev(ctx.handle, n, q, dU.ptr, n, dA.ptr, q, dO.ptr, ldx), "pg_rotate_dev")
-    ctx.sync()
-    out = dO.download((q, ldx), np.float32)[:, :n].T.copy()
-    dA.free(); dO.free()
-    return out
+    with _lib.scope(ctx):
+        dA = ctx.to_device(np.ascontiguousarray(A, np.float32))
+        dO = ctx.alloc(q * ldx * 4)
+        _lib.check(L.pg_rotate_dev(ctx.handle, n, q, dU.ptr, n, dA.ptr, q, dO.ptr, ldx), "pg_rotate_dev")
+        ctx.sync()
+        return dO.download((q, ldx), np.float32)[:, :n].T.copy()
 
 
 _COLS = ("beta", "se_beta", "tau", "lambda", "F_wald", "p_wald")
@@ -591,7 +590,7 @@ def kinship(G, standardize=True, device=0, *, snp_batch=None):
     L = _lib.load()
     G = np.ascontiguousarray(G, np.float32)
     n, p = G.shape
-    with _lib.Context(device) as ctx:
+    with _lib.scope(device=device) as ctx:
         dG = ctx.to_device(G)
         dK = ctx.alloc(n * n * 4)
         _lib.check(L.pg_kinship_geno_dev(ctx.handle, n, p, dG.ptr, p, int(bool(standardize)), dK.ptr), "pg_kinship_geno_dev")
@@ -693,14 +692,11 @@ def _zkzt(L, Z, K):
         return np.ascontiguousarray(a)
     Z, K = dev_ready(Z), dev_ready(K)
     n, q = Z.shape
-    with _lib.Context(0) as ctx:
+    with _lib.scope() as ctx:
         dZ, dK, dO = ctx.to_device(Z), ctx.to_device(K), ctx.alloc(n * n * 4)
         _lib.check(L.pg_zkzt_dev(ctx.handle, n, q, dZ.ptr, int(Z.dtype == np.float64), q, dK.ptr, int(K.dtype == np.float64), q, dO.ptr, n),
                    "pg_zkzt_dev")
-        out = dO.download((n, n), np.float32)
-        for b_ in (dZ, dK, dO):
-            b_.free()
-    return out
+        return dO.download((n, n), np.float32)
 
 
 def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=False, grid=False, eigen=True, nproc=1,
@@ -860,7 +856,7 @@ def pygemma_gxe(Y, X, W, K, E, Z=None, snps=None, verbose=0, disable_checks=True
 
 def _null_lambda(L, n, c, d, Wr, yr):
     """lambda0 of the score test: the ML lambda of y ~ W on GPU 0 (pg_score_null_dev), read back as one float32."""
-    with _lib.Context(0) as ctx:
+    with _lib.scope() as ctx:
         dd, dW, dy, dl = ctx.to_device(d), ctx.to_device(Wr), ctx.to_device(yr), ctx.alloc(4)
         _lib.check(L.pg_score_null_dev(ctx.handle, n, c, dd.ptr, dW.ptr, dy.ptr, dl.ptr), "pg_score_null_dev")
         ctx.sync()

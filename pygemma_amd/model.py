@@ -31,10 +31,6 @@ def _f32(a):
     return np.ascontiguousarray(a, np.float32)
 
 
-def _ctx(ctx):
-    return (ctx, False) if ctx is not None else (_lib.Context(0), True)
-
-
 def precompute_mat(lam, eigenVals, W, Y, full=False, ctx=None):
     """pyx:880.  W (n, c) with the SNP as last column, Y (n,1).  Entries the reference leaves undefined
     (its arrays come from np.empty) are NaN here."""
@@ -42,8 +38,7 @@ def precompute_mat(lam, eigenVals, W, Y, full=False, ctx=None):
     d, Wx, y = _f32(eigenVals).reshape(-1), _f32(W), _f32(np.asarray(Y).reshape(-1))
     n, ctot = Wx.shape
     m = ctot + 1
-    ctx, own = _ctx(ctx)
-    try:
+    with _lib.scope(ctx) as ctx:
         dd, dW, dy = ctx.to_device(d), ctx.to_device(Wx), ctx.to_device(y)
         dP, dQ, dR = (ctx.alloc(m * m * m * 4) for _ in range(3))
         dv, ds = ctx.alloc(5 * m * 4), ctx.alloc(8 * 4)
@@ -52,11 +47,6 @@ def precompute_mat(lam, eigenVals, W, Y, full=False, ctx=None):
         ctx.sync()
         P3, Q3, R3 = (b.download((m, m, m), np.float32) for b in (dP, dQ, dR))
         vecs, scal = dv.download((5, m), np.float32), ds.download((8,), np.float32)
-        for b in (dd, dW, dy, dP, dQ, dR, dv, ds):
-            b.free()
-    finally:
-        if own:
-            ctx.close()
     out = {"wjt_Pi_wk": P3, "wjt_Pi_Pi_wk": Q3[:ctot, :, :ctot], "tr_Pi": vecs[3], "yt_Pi_y": vecs[0], "yt_Pi_Pi_y": vecs[1],
            "logdet_Wt_W": 0.0, "logdet_Wt_H_inv_W": float(scal[0]), "logdet_H": float(scal[1])}
     if full:
@@ -68,18 +58,12 @@ def precompute_mat(lam, eigenVals, W, Y, full=False, ctx=None):
 
 def _scalars(n, c, lam=1.0, yPy=1.0, yPPy=1.0, yPPPy=1.0, trP=0.0, trPP=0.0, ldH=0.0, ld=0.0, ctx=None):
     L = _lib.load()
-    ctx, own = _ctx(ctx)
-    try:
+    with _lib.scope(ctx) as ctx:
         a = np.array([lam, yPy, yPPy, yPPPy, trP, trPP, ldH, ld], np.float32)
         da, do = ctx.to_device(a), ctx.alloc(3 * 4)
         _lib.check(L.pg_reml_scalars_dev(ctx.handle, int(n), int(c), da.ptr, do.ptr), "pg_reml_scalars_dev")
         ctx.sync()
-        out = do.download((3,), np.float32)
-        da.free(); do.free()
-        return out
-    finally:
-        if own:
-            ctx.close()
+        return do.download((3,), np.float32)
 
 
 def likelihood_restricted_lambda_overload(lam, n, c, yt_Px_y, logdet_H, logdet_Wt_W, logdet_Wt_H_inv_W, ctx=None):
@@ -113,19 +97,12 @@ def newton(lam, eigenVals, Y, W, precompute=True, lambda_min=1e-5, lambda_max=1e
     L = _lib.load()
     d, Wx, y = _f32(eigenVals).reshape(-1), _f32(W), _f32(np.asarray(Y).reshape(-1))
     n, ctot = Wx.shape
-    ctx, own = _ctx(ctx)
-    try:
+    with _lib.scope(ctx) as ctx:
         dd, dW, dy, do = ctx.to_device(d), ctx.to_device(Wx), ctx.to_device(y), ctx.alloc(4)
         _lib.check(L.pg_newton_dev(ctx.handle, n, ctot, float(np.float32(lam)), float(np.float32(lambda_min)),
                                    float(np.float32(lambda_max)), dd.ptr, dW.ptr, dy.ptr, do.ptr), "pg_newton_dev")
         ctx.sync()
-        out = do.download((1,), np.float32)[0]
-        for b in (dd, dW, dy, do):
-            b.free()
-        return float(out)
-    finally:
-        if own:
-            ctx.close()
+        return float(do.download((1,), np.float32)[0])
 
 
 def calc_lambda_restricted(eigenVals, Y, W, precompute=True, grid=False, ctx=None):
@@ -164,8 +141,7 @@ def _ml_scalars(lam, eigenVals, Y, W, full, ctx=None):
     L = _lib.load()
     Wx = _f32(W)
     n, ctot = Wx.shape
-    ctx, own = _ctx(ctx)
-    try:
+    with _lib.scope(ctx) as ctx:
         r = precompute_mat(lam, eigenVals, Wx, Y, full=full, ctx=ctx)
         yPy, yPPy = r["yt_Pi_y"][ctot], r["yt_Pi_Pi_y"][ctot]
         yPPPy = r["yt_Pi_Pi_Pi_y"][ctot] if full else np.float32(0)
@@ -174,13 +150,9 @@ def _ml_scalars(lam, eigenVals, Y, W, full, ctx=None):
         _lib.check(L.pg_ml_scalars_dev(ctx.handle, n, da.ptr, do.ptr), "pg_ml_scalars_dev")
         ctx.sync()
         out = do.download((3,), np.float32)
-        da.free(); do.free()
         if not full:
             out[2] = np.nan
         return out
-    finally:
-        if own:
-            ctx.close()
 
 
 def likelihood_lambda(lam, eigenVals, Y, W, ctx=None):
@@ -204,8 +176,7 @@ def calc_lambda(eigenVals, Y, W, ctx=None):
     candidates, the one with the largest likelihood_lambda returned.  Same SciPy calls as the reference, the functions evaluated on
     the device.  (lmm.pygemma(..., lrt=True) runs this search inside the association kernel for every SNP at once.)"""
     from scipy import optimize
-    ctx, own = _ctx(ctx)
-    try:
+    with _lib.scope(ctx) as ctx:
         d1 = lambda l: likelihood_derivative1_lambda(l, eigenVals, Y, W, ctx)                    # noqa: E731
         d2 = lambda l: likelihood_derivative2_lambda(l, eigenVals, Y, W, ctx)                    # noqa: E731
         roots = [np.power(10.0, -5.0), np.power(10.0, 5.0)]
@@ -220,6 +191,3 @@ def calc_lambda(eigenVals, Y, W, ctx=None):
                 roots.append(root)
         ll = [likelihood_lambda(lam, eigenVals, Y, W, ctx) for lam in roots]
         return roots[int(np.argmax(ll))]
-    finally:
-        if own:
-            ctx.close()

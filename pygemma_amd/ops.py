@@ -14,9 +14,7 @@ def assoc(d, Wr, yr, Xr, grid=False, ctx=None, want_p=True, return_stats=False):
     """calculate((eigenVals, Y, W, X_block, grid)) (lmm/lmm.py:461) on the GPU.
     d (n,), Wr (n,c), yr (n,) or (n,1), Xr (n,p) in the REFERENCE layout, all in the eigenbasis."""
     L = _lib.load()
-    own = ctx is None
-    ctx = ctx or _lib.Context(0)
-    try:
+    with _lib.scope(ctx) as ctx:
         d, Wr, yr, Xr = _f32(d), _f32(Wr), _f32(np.asarray(yr).reshape(-1)), _f32(Xr)
         n, c = Wr.shape
         p = Xr.shape[1]
@@ -32,9 +30,6 @@ def assoc(d, Wr, yr, Xr, grid=False, ctx=None, want_p=True, return_stats=False):
         if return_stats:
             out["n_evals"] = stats.astype(np.int64)
         return out
-    finally:
-        if own:
-            ctx.close()
 
 
 def score(d, Wr, yr, Xr, lam0=None, ctx=None):
@@ -43,9 +38,7 @@ def score(d, Wr, yr, Xr, lam0=None, ctx=None):
     evaluate at (None: the ML lambda of y ~ W, computed on the device).  Returns dict(beta, se_beta, tau, lambda, F_score,
     p_score, lambda_null)."""
     L = _lib.load()
-    own = ctx is None
-    ctx = ctx or _lib.Context(0)
-    try:
+    with _lib.scope(ctx) as ctx:
         d, Wr, yr, Xr = _f32(d), _f32(Wr), _f32(np.asarray(yr).reshape(-1)), _f32(Xr)
         n, c = Wr.shape
         p = Xr.shape[1]
@@ -56,7 +49,6 @@ def score(d, Wr, yr, Xr, lam0=None, ctx=None):
             _lib.check(L.pg_score_null_dev(ctx.handle, n, c, dd.ptr, dW.ptr, dy.ptr, dl.ptr), "pg_score_null_dev")
             ctx.sync()
             lam0 = dl.download((1,), np.float32)[0]
-            dl.free()
         lam0 = np.float32(lam0)
         dX = ctx.to_device(Xr)
         dXr = ctx.alloc(max(p, 1) * n * 4)
@@ -70,12 +62,7 @@ def score(d, Wr, yr, Xr, lam0=None, ctx=None):
                for k, (col, b) in enumerate(zip(("beta", "se_beta", "tau", "lambda", "F_score", "p_score"), out))}
         res["lambda"] = res["lambda"].astype(np.float64)
         res["lambda_null"] = float(lam0)
-        for b in (dd, dW, dy, dX, dXr, *out):
-            b.free()
         return res
-    finally:
-        if own:
-            ctx.close()
 
 
 def gxe(d, Wr, yr, Xr, XEr, ctx=None, want_p=True, return_stats=False):
@@ -85,9 +72,7 @@ def gxe(d, Wr, yr, Xr, XEr, ctx=None, want_p=True, return_stats=False):
     layout, all in the eigenbasis.  Returns dict(beta, se_beta, tau, lambda, F_wald, p_wald[, n_evals]); beta is beta_gxe and
     p_wald uses F(1, n - c - 2)."""
     L = _lib.load()
-    own = ctx is None
-    ctx = ctx or _lib.Context(0)
-    try:
+    with _lib.scope(ctx) as ctx:
         d, Wr, yr, Xr, XEr = _f32(d), _f32(Wr), _f32(np.asarray(yr).reshape(-1)), _f32(Xr), _f32(XEr)
         n, c = Wr.shape
         p = Xr.shape[1]
@@ -111,37 +96,25 @@ def gxe(d, Wr, yr, Xr, XEr, ctx=None, want_p=True, return_stats=False):
             res["p_wald"] = None
         if return_stats:
             res["n_evals"] = dst.download((2,), np.uint64).astype(np.int64)
-        for b in (dd, dW, dy, dX, dXE, dXr, dXEr, dst, *out):
-            b.free()
         return res
-    finally:
-        if own:
-            ctx.close()
 
 
 def fdist_sf(F, dfd, ctx=None):
     L = _lib.load()
-    own = ctx is None
-    ctx = ctx or _lib.Context(0)
-    try:
+    with _lib.scope(ctx) as ctx:
         F = np.ascontiguousarray(F, np.float64).ravel()
         dF = ctx.to_device(F)
         dP = ctx.alloc(F.nbytes)
         _lib.check(L.pg_fdist_sf_dev(ctx.handle, F.size, dF.ptr, float(dfd), dP.ptr), "pg_fdist_sf_dev")
         ctx.sync()
         return dP.download(F.shape, np.float64)
-    finally:
-        if own:
-            ctx.close()
 
 
 def rotate(U, X, ctx=None, ldx=None):
     """X <- U' X (lmm/lmm.py:243-246) on the GPU; U (n,n) eigenvectors in columns, X (n,p).
     Returns the SNP-major rotated block (p, ldx) float32."""
     L = _lib.load()
-    own = ctx is None
-    ctx = ctx or _lib.Context(0)
-    try:
+    with _lib.scope(ctx) as ctx:
         U, X = _f32(U), _f32(X)
         n, p = X.shape
         ldx = ldx or (n + 63) // 64 * 64
@@ -149,22 +122,14 @@ def rotate(U, X, ctx=None, ldx=None):
         dXr = ctx.alloc(p * ldx * 4)
         _lib.check(L.pg_rotate_dev(ctx.handle, n, p, dU.ptr, n, dX.ptr, p, dXr.ptr, ldx), "pg_rotate_dev")
         ctx.sync()
-        out = dXr.download((p, ldx), np.float32)
-        for b in (dU, dX, dXr):
-            b.free()
-        return out
-    finally:
-        if own:
-            ctx.close()
+        return dXr.download((p, ldx), np.float32)
 
 
 def syevd(K, ctx=None, want64=False):
     """scipy.linalg.eigh(K) (lmm/lmm.py:152) on the GPU: lower triangle of K (n,n) float32 ->
     (evals f32 ascending clamped >= 0, U f32 with eigenvector j in column j[, evals f64, U f64])."""
     L = _lib.load()
-    own = ctx is None
-    ctx = ctx or _lib.Context(0)
-    try:
+    with _lib.scope(ctx) as ctx:
         K = _f32(K)
         n = K.shape[0]
         assert K.shape == (n, n)
@@ -178,22 +143,14 @@ def syevd(K, ctx=None, want64=False):
         out = [dev.download((n,), np.float32), dU.download((n, n), np.float32)]
         if want64:
             out += [d64.download((n,), np.float64), U64.download((n, n), np.float64)]
-        for b in (dK, dev, dU, d64, U64):
-            if b is not None:
-                b.free()
         return tuple(out)
-    finally:
-        if own:
-            ctx.close()
 
 
 def rotate_geno(U, X, ctx=None, ldx=None):
     """Genotype fast path of X <- U'X (pg_rotate_geno_dev).  Returns (Xr (p, ldx) float32, True) when every column of X
     takes <= 3 equally spaced values, else (None, False)."""
     L = _lib.load()
-    own = ctx is None
-    ctx = ctx or _lib.Context(0)
-    try:
+    with _lib.scope(ctx) as ctx:
         U, X = _f32(U), _f32(X)
         n, p = X.shape
         ldx = ldx or (n + 63) // 64 * 64
@@ -206,21 +163,14 @@ def rotate_geno(U, X, ctx=None, ldx=None):
         _lib.check(L.pg_rotate_geno_dev(ctx.handle, n, p, dprep.ptr, dX.ptr, p, dXr.ptr, ldx, dwork.ptr, C.byref(ok)), "pg_rotate_geno_dev")
         ctx.sync()
         out = dXr.download((p, ldx), np.float32) if ok.value else None
-        for b in (dU, dX, dprep, dwork, dXr):
-            b.free()
         return out, int(ok.value)     # 1: genotype-valued block, 2: general finite block (X split in two fp16 planes)
-    finally:
-        if own:
-            ctx.close()
 
 
 def rotate_auto(U, X, ctx=None):
     """pg_rotate_auto_dev: the rotation of a float32 block with the path (genotype fp16x2 / split planes / fp32 MFMA for NaN
     blocks) chosen on the device.  Returns (Xr (p, ldx) float32, path) with path 1 / 2 / 0 like pg_rotate_geno_dev's flag."""
     L = _lib.load()
-    own = ctx is None
-    ctx = ctx or _lib.Context(0)
-    try:
+    with _lib.scope(ctx) as ctx:
         U, X = _f32(U), _f32(X)
         n, p = X.shape
         ldx = (n + 63) // 64 * 64
@@ -231,10 +181,4 @@ def rotate_auto(U, X, ctx=None):
         _lib.check(L.pg_rotate_auto_dev(ctx.handle, n, p, dU.ptr, n, dprep.ptr, dX.ptr, p, dXr.ptr, ldx, dwork.ptr, dpath.ptr),
                    "pg_rotate_auto_dev")
         ctx.sync()
-        out = dXr.download((p, ldx), np.float32), int(dpath.download((1,), np.int32)[0])
-        for b in (dU, dX, dprep, dwork, dXr, dpath):
-            b.free()
-        return out
-    finally:
-        if own:
-            ctx.close()
+        return dXr.download((p, ldx), np.float32), int(dpath.download((1,), np.int32)[0])

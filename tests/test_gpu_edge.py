@@ -203,3 +203,43 @@ def test_every_entry_point_rejects_bad_arguments_before_any_launch(ctx):
     rp = synth.rotated_panel(n, p, c, seed=3)
     got = ops.assoc(rp["d"], rp["W"], rp["Y"], rp["X"], ctx=ctx)
     assert np.isfinite(got["beta"]).all()
+
+
+def test_wrappers_leave_a_borrowed_context_as_they_found_it():
+    """Every one-shot wrapper frees what it allocated on the caller's context and unlists it — also when the library refuses the
+    call — and touches nothing the caller allocated (_lib.scope)."""
+    from pygemma_amd import _lib, model, ops, synth
+    n, p, c = 64, 8, 2
+    rp = synth.rotated_panel(n, p, c, seed=11)
+    raw = synth.panel(n, p, c, seed=11)
+    d, W, Y, X = rp["d"], rp["W"], rp["Y"], rp["X"]
+    rng = np.random.default_rng(11)
+    XE = (X * rng.standard_normal((n, 1))).astype(np.float32)
+    U = np.linalg.qr(rng.standard_normal((n, n)))[0].astype(np.float32)
+    G = rng.integers(0, 3, size=(n, p)).astype(np.float32)
+    Wx = np.ascontiguousarray(np.c_[W, X[:, :1]])
+    with _lib.Context(0) as ctx:
+        mine = ctx.to_device(np.arange(16, dtype=np.float32))
+        before = list(ctx._bufs)
+        assert before == [mine]
+        calls = [("assoc", lambda: ops.assoc(d, W, Y, X, ctx=ctx)),
+                 ("score", lambda: ops.score(d, W, Y, X, ctx=ctx)),
+                 ("gxe", lambda: ops.gxe(d, W, Y, X, XE, ctx=ctx, return_stats=True)),
+                 ("rotate", lambda: ops.rotate(U, G, ctx=ctx)),
+                 ("rotate_geno", lambda: ops.rotate_geno(U, G, ctx=ctx)),
+                 ("rotate_auto", lambda: ops.rotate_auto(U, G, ctx=ctx)),
+                 ("fdist_sf", lambda: ops.fdist_sf(np.linspace(0.1, 9.0, p), n - c - 1, ctx=ctx)),
+                 ("syevd", lambda: ops.syevd(raw["K"], ctx=ctx, want64=True)),
+                 ("precompute_mat", lambda: model.precompute_mat(1.0, d, Wx, Y, full=True, ctx=ctx)),
+                 ("newton", lambda: model.newton(1.0, d, Y, Wx, ctx=ctx))]
+        for name, call in calls:
+            call()
+            assert ctx._bufs == before, (name, len(ctx._bufs))
+        # refused by the argument check (c + 1 > PG_MAX_COVARIATES) after the wrapper has allocated its buffers, before any launch
+        with pytest.raises(_lib.PgError, match="not supported"):
+            ops.gxe(d, np.ones((n, 30), np.float32), Y, X, XE, ctx=ctx)
+        assert ctx._bufs == before
+        assert mine.ptr is not None
+        np.testing.assert_array_equal(mine.download((16,), np.float32), np.arange(16, dtype=np.float32))
+        mine.free()
+        assert ctx._bufs == [] and mine.ptr is None

@@ -1,5 +1,5 @@
 """CPU-only checks of the boundary: the C-ABI library loads and exports every symbol include/pygemma_hip.h
-declares (no compute without a GPU), the host logic mirrors the reference's (SampleIter split, casts, error
+declares (no compute without a GPU), every function is bound with the signature the header declares, the host logic mirrors the reference's (SampleIter split, casts, error
 behaviour), and the product never reaches for the oracle."""
 import os
 import re
@@ -33,6 +33,93 @@ def test_library_exports_every_declared_symbol():
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith(("pg_", "pgx_"))}
     assert exported <= set(decl), sorted(exported - set(decl))
+
+
+def _loaded():
+    from pygemma_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return _lib, _lib.load()
+
+
+def test_every_declared_function_is_bound_with_its_parameter_count():
+    """Counted here independently of _lib's parser: the names in header order, the commas of every parameter list."""
+    _lib, L = _loaded()
+    hdr = open(os.path.join(ROOT, "include", "pygemma_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    decl = re.findall(r"\b(pgx?_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)
+    assert len(decl) >= 89 and [name for name, _ in decl] == _lib.SYMBOLS
+    for name, params in decl:
+        f = getattr(L, name)
+        assert f.argtypes is not None, f"{name}: no argtypes"
+        assert len(f.argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), name
+
+
+def test_pinned_signatures_one_per_type_class():
+    """Written out by hand from include/pygemma_hip.h."""
+    import ctypes as C
+    _lib, L = _loaded()
+    vp, i64, i32, sz, f32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_float, C.c_double
+    pinned = {
+        "pg_assoc_dev": (i32, [vp, i64, i32, i64, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "pg_score_dev": (i32, [vp, i64, i32, i64, vp, vp, vp, f32, vp, i64, vp, vp, vp, vp, vp, vp]),
+        "pgx_dgemm_ex_dev": (i32, [vp, i32, i32, i64, i64, i64, f64, vp, i64, vp, i64, f64, vp, i64]),
+        "pg_memcpy2d_h2d_async": (i32, [vp, vp, sz, vp, sz, sz, sz]),
+        "pg_geno_prep_bytes": (sz, [i64]),
+        "pg_ctx_destroy": (None, [vp]),
+        "pg_last_error": (C.c_char_p, []),
+        "pg_comm_init_all": (i32, [i32, vp, vp]),              # pg_ctx *const *, pg_comm **
+        "pg_stage_rows": (i32, [vp, sz, vp, sz, sz, sz, i32]),  # no context argument
+        "pgx_ring_stamps": (i32, [vp]),                         # long long *
+    }
+    assert len(pinned["pg_assoc_dev"][1]) == 17
+    for name, (restype, argtypes) in pinned.items():
+        f = getattr(L, name)
+        assert f.restype is restype, (name, f.restype)
+        assert list(f.argtypes) == argtypes, (name, f.argtypes)
+
+
+def test_header_parser_on_a_text_of_its_own():
+    import ctypes as C
+    from pygemma_amd import _lib
+    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
+    text = """
+    #ifdef __cplusplus
+    extern "C" {
+    #endif
+    #define PG_X (-1)   /* pg_not_a_call(int) */
+    typedef struct pg_ctx pg_ctx;
+    enum { PG_A = 0, PG_B = 1 };
+    int pg_init_all(int ndev, pg_ctx *const *ctxs, pg_comm **out /* [ndev] */);
+    int pg_three(pg_ctx *ctx, int64_t n,
+                 const float *d, unsigned long long *stats,
+                 double alpha);   /* pg_in_a_comment(int x); */
+    size_t pgx_bytes(int64_t n);
+    const char *pg_text(void);
+    void pg_close(pg_ctx *ctx);
+    #ifdef __cplusplus
+    }
+    #endif
+    """
+    assert _lib.parse_header(text) == [("pg_init_all", i32, [i32, vp, vp]), ("pg_three", i32, [vp, i64, vp, vp, C.c_double]),
+                                       ("pgx_bytes", C.c_size_t, [i64]), ("pg_text", C.c_char_p, []), ("pg_close", None, [vp])]
+    # a type outside the table is an error that names the function and the type, never ctypes' default int
+    for bad, ctype in (("int pg_bad(pg_ctx *ctx, long double x);", "long double"), ("long double pg_bad(void);", "long double"),
+                       ("int pg_bad(unsigned n);", "unsigned"), ("int pg_bad(long long n);", "long long"), ("pg_bad(int n);", "")):
+        with pytest.raises(_lib.PgError, match=f"pg_bad: C type '{ctype}'"):
+            _lib.parse_header(bad)
+    with pytest.raises(_lib.PgError, match="pg_bad: C type 'long double'"):
+        _lib.parse_header(text.replace("size_t pgx_bytes", "int pg_bad(long double x);\n    size_t pgx_bytes"))
+
+
+def test_missing_header_is_an_error_with_its_path(monkeypatch, tmp_path):
+    _lib, _ = _loaded()
+    gone = str(tmp_path / "include" / "pygemma_hip.h")
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "HEADER", gone)
+    with pytest.raises(_lib.PgError, match=re.escape(gone)):
+        _lib.load()
 
 
 def test_no_gpu_means_loud_failure_not_fallback():

@@ -6,7 +6,6 @@ import numpy as np
 sys.path.insert(0, '/root/repo')
 from pygemma_amd import _lib
 L = _lib.load(); ctx = _lib.Context(0)
-L.pgx_ring_stamps.argtypes = [C.c_void_p]
 rng = np.random.default_rng(0)
 which = sys.argv[1] if len(sys.argv) > 1 else "update"
 m = 9984

@@ -5,7 +5,6 @@ import numpy as np
 sys.path.insert(0, '/root/repo')
 from pygemma_amd import _lib
 L = _lib.load(); ctx = _lib.Context(0)
-L.pgx_ring_stamps.argtypes = [C.c_void_p]
 rng = np.random.default_rng(0)
 st = (C.c_longlong * 64)(); _lib.check(L.pgx_ring_stamps(st), "stamps")
 n = 4096
