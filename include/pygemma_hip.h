@@ -130,6 +130,12 @@ int pg_assoc_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, const
  * pg_assoc_dev calls on this context write, per SNP, fast evaluations | full (Newton) evaluations << 16 into trace_dev
  * (device, >= p entries, caller-owned); NULL switches the trace off. */
 int pg_assoc_set_eval_trace(pg_ctx *ctx, unsigned *trace_dev);
+/* Which passes over the n elements the SNP-specific evaluations (Brent, Newton, the one at the root) took: the following
+ * pg_assoc_dev calls on this context add, summed over their SNPs, to dev4[0..3] (device, caller-owned, caller-zeroed) the passes
+ * that produced the Gram power P, those that produced Q, those that produced R — a fused pass counts once for each power it
+ * produces, the decade scan is not counted — and the Newton starts that reused Brent's P and Q; NULL switches it off.  The
+ * evaluation counts of pg_assoc_dev's stats do not depend on it: those count evaluations, not passes. */
+int pg_assoc_set_pass_stats(pg_ctx *ctx, unsigned long long *dev4);
 /* Optional: what the FIRST pg_assoc_dev / pg_assoc_lrt_dev call of a context does on the host before it can enqueue its kernels (the
  * float32-sum plan of numpy's add.reduce for length n: built on the host, uploaded after a stream drain; scratch allocations for c
  * covariates) — ahead of time.  A streaming caller (lmm/lmm.py:461-495's per-SNP loop cut into batches) calls it while its first batch is

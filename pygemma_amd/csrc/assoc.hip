@@ -62,13 +62,26 @@ constexpr int WPB = PG_ASSOC_WPB;
 #ifndef PG_WAVES
 #define PG_WAVES 2          // waves per SIMD the register allocation is held to
 #endif
+// Gram powers the result does not need (each its own switch, so that a stage can be timed and dropped alone):
+#ifndef PG_ASSOC_FINAL_P
+#define PG_ASSOC_FINAL_P 1        // the evaluation at the root feeds logL, beta and se only: P alone, no Q
+#endif
+#ifndef PG_ASSOC_NEWTON_REUSE
+#define PG_ASSOC_NEWTON_REUSE 1   // Newton's first evaluation takes P, Q and t1 from Brent when it starts at a lambda Brent evaluated: R alone
+#endif
+#ifndef PG_REUSE_MAX_SLOTS
+#define PG_REUSE_MAX_SLOTS 4      // ... while a lane owns at most this many Gram entries per power (c <= 20): 9 KiB of LDS per wave at 4
+#endif
 
 // Per-wave dynamic LDS of assoc_kernel — ONE definition for the kernel's carve-up and the host's launch size, so the two
-// cannot drift apart: [piv: 3 M doubles when the sweeps exchange their pivot column through LDS] | xent[NLAM][2M] doubles |
+// cannot drift apart: [piv: 3 M doubles when the sweeps exchange their pivot column through LDS] | [sav: Brent's last two
+// evaluations, every lane's P[slots], Q[slots] and t1, where Newton reuses them (sav_slots = 0: nowhere)] | xent[NLAM][2M] doubles |
 // evs[NLAM] | d1s[NLAM] | lls[NLAM] | vals[n_vals], rounded up to 16 bytes.
-__host__ __device__ constexpr size_t assoc_per_wave_bytes(int M, bool sweep_lds, size_t evalout_bytes, int n_vals)
+__host__ __device__ constexpr size_t assoc_sav_doubles(int sav_slots) { return sav_slots ? (size_t)2 * (2 * sav_slots + 1) * 64 : 0; }
+__host__ __device__ constexpr size_t assoc_per_wave_bytes(int M, bool sweep_lds, int sav_slots, size_t evalout_bytes, int n_vals)
 {
-    return (((sweep_lds ? (size_t)3 * M * 8 : 0) + (size_t)NLAM * 2 * M * 8 + NLAM * evalout_bytes + 2 * NLAM * 4 + (size_t)n_vals * 4) + 15) & ~(size_t)15;
+    return (((sweep_lds ? (size_t)3 * M * 8 : 0) + assoc_sav_doubles(sav_slots) * 8 + (size_t)NLAM * 2 * M * 8 + NLAM * evalout_bytes + 2 * NLAM * 4 +
+             (size_t)n_vals * 4) + 15) & ~(size_t)15;
 }
 
 struct AssocParams {
@@ -88,6 +101,7 @@ struct AssocParams {
     double *F;
     unsigned long long *stats;
     unsigned *trace;       // optional: per SNP, fast evaluations | full (Newton) evaluations << 16 (pg_assoc_set_eval_trace)
+    unsigned long long *passes;   // optional: passes over n that produced P | Q | R, Newton starts on Brent's P and Q (pg_assoc_set_pass_stats)
     // N2 (LRT instantiations only): ML lambda and log-likelihood per SNP; ml_c = f32(f32((n/2) ln(n/2pi)) - (n/2)) (pyx:1552-1554)
     int lrt, nhalf;
     float ml_c;
@@ -283,7 +297,13 @@ template <int C> struct Shape {
     static constexpr int G = (SCAN_NV / (2 * M)) < 1 ? 1 : ((SCAN_NV / (2 * M)) > 11 ? 11 : (SCAN_NV / (2 * M)));
     // powers accumulated per pass over n: fused while the accumulators fit the register budget of 2 waves/SIMD
     static constexpr bool FUSE_PQ = NP <= PG_FUSE_PQ_MAX, FUSE_PQR = NP <= PG_FUSE_PQR_MAX;
+    // Newton's first evaluation on Brent's P and Q, kept in the wave's LDS (2 SLOTS + 1 doubles per lane and evaluation): up to
+    // PG_REUSE_MAX_SLOTS, beyond which the two kept evaluations would cost the 8 waves of a CU more than half of its LDS
+    static constexpr bool NEWTON_REUSE = PG_ASSOC_NEWTON_REUSE && SLOTS <= PG_REUSE_MAX_SLOTS;
+    static constexpr int SAV_SLOTS = NEWTON_REUSE ? SLOTS : 0, SAV_STRIDE = (2 * SLOTS + 1) * 64;   // doubles per kept evaluation
 };
+// the powers of an evaluation, as the MASK of gram_pass: P | Q | R
+constexpr int PW_P = 1, PW_PQ = 3, PW_R = 4, PW_PQR = 7;
 __host__ __device__ constexpr int tri(int r, int c) { return r * (r + 1) / 2 + c; }  // r >= c
 __host__ __device__ constexpr int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
@@ -360,11 +380,16 @@ __device__ __forceinline__ void wave_lds_sync();
 // The c_tot sweeps of precompute_mat (pyx:947-963 / :1007-1036) with the Gram entries spread over the lanes:
 // every lane updates the entry (r,c) it owns, fetching the pivot-column operands from their owners; arithmetic per
 // entry identical to oracle sweeps(order=1).  Scalars (traces, pivots) are wave-uniform.
-template <int C, bool FULL>
+// PW: the powers swept (PW_P, PW_PQ or PW_PQR).  Every power's update reads itself and the lower powers only, and the pivots,
+// their logs and the clamps of P are P's own: sweeping fewer powers leaves the bits of those swept as they are.  PW_P exports
+// yPy, ld, Pxx_c, Pyx_c and sh; the fields of a power that is not swept are 0 and must not be read.
+template <int C, int PW>
 __device__ __forceinline__ void lane_sweeps(double (&P)[Shape<C>::SLOTS], double (&Q)[Shape<C>::SLOTS], double (&R)[Shape<C>::SLOTS],
                                             const Own<C> &own, double t1, double t2, int lane, EvalOut &o, double *piv)
 {
     constexpr int M = Shape<C>::M, NP = Shape<C>::NP, SLOTS = Shape<C>::SLOTS;
+    static_assert(PW == PW_P || PW == PW_PQ || PW == PW_PQR, "powers");
+    constexpr bool DQ = (PW & 2) != 0, FULL = (PW & 4) != 0;
     // With three or more slots per lane (c >= 14) the pivot column goes through the wave's LDS (piv: 3 M doubles) instead of
     // lane shuffles: a shuffle-gather costs SLOTS permutes per operand, 6 SLOTS^2 per step — pure data movement either way.
     constexpr bool VIA_LDS = Shape<C>::SWEEP_LDS;
@@ -372,43 +397,46 @@ __device__ __forceinline__ void lane_sweeps(double (&P)[Shape<C>::SLOTS], double
     double trP = t1, trPP = t2, apiv = 1.0;
     for (int i = 1; i < M; i++) {
         const int q = i - 1, eqq = tri(q, q);
-        double a, b, e = 0.0;
+        double a, b = 0.0, e = 0.0;
         double ur[SLOTS], uc[SLOTS], vr[SLOTS], vc[SLOTS], wr[SLOTS], wc[SLOTS];
         bool act[SLOTS];
         if constexpr (VIA_LDS) {
 #pragma unroll
             for (int sl = 0; sl < SLOTS; sl++)
                 if (own.valid[sl] && own.c[sl] == q) {       // owners of column q publish it (replicas write the same value)
-                    piv[own.r[sl]] = P[sl]; piv[M + own.r[sl]] = Q[sl];
+                    piv[own.r[sl]] = P[sl];
+                    if (DQ) piv[M + own.r[sl]] = Q[sl];
                     if (FULL) piv[2 * M + own.r[sl]] = R[sl];
                 }
             wave_lds_sync();
-            a = piv[q]; b = piv[M + q];
+            a = piv[q];
+            if (DQ) b = piv[M + q];
             if (FULL) e = piv[2 * M + q];
 #pragma unroll
             for (int sl = 0; sl < SLOTS; sl++) {
                 act[sl] = own.valid[sl] && own.c[sl] >= i;
                 const int rr = act[sl] ? own.r[sl] : q, cc = act[sl] ? own.c[sl] : q;
                 ur[sl] = piv[rr]; uc[sl] = piv[cc];
-                vr[sl] = piv[M + rr]; vc[sl] = piv[M + cc];
+                if (DQ) { vr[sl] = piv[M + rr]; vc[sl] = piv[M + cc]; }
                 if (FULL) { wr[sl] = piv[2 * M + rr]; wc[sl] = piv[2 * M + cc]; }
             }
             wave_lds_sync();                                  // all reads done before the next step's writes
         } else {
-            a = gather<SLOTS>(P, eqq); b = gather<SLOTS>(Q, eqq);
-            e = FULL ? gather<SLOTS>(R, eqq) : 0.0;
+            a = gather<SLOTS>(P, eqq);
+            if (DQ) b = gather<SLOTS>(Q, eqq);
+            if (FULL) e = gather<SLOTS>(R, eqq);
 #pragma unroll
             for (int sl = 0; sl < SLOTS; sl++) {
                 act[sl] = own.valid[sl] && own.c[sl] >= i;       // r >= c >= i
                 const int er = act[sl] ? tri(own.r[sl], q) : 0, ec = act[sl] ? tri(own.c[sl], q) : 0;
                 ur[sl] = gather<SLOTS>(P, er); uc[sl] = gather<SLOTS>(P, ec);
-                vr[sl] = gather<SLOTS>(Q, er); vc[sl] = gather<SLOTS>(Q, ec);
+                if (DQ) { vr[sl] = gather<SLOTS>(Q, er); vc[sl] = gather<SLOTS>(Q, ec); }
                 if (FULL) { wr[sl] = gather<SLOTS>(R, er); wc[sl] = gather<SLOTS>(R, ec); }
             }
         }
         if (lane == q) apiv = a;
         const double a2 = a * a, ia = -1.0 / a, ba2 = b / a2;
-        if (FULL) {
+        if constexpr (FULL) {
             const double ba = b / a;
             trPP = (trPP + ba * ba) - 2 * (e / a);
             const double a3 = a2 * a, b2 = b * b;
@@ -425,17 +453,27 @@ __device__ __forceinline__ void lane_sweeps(double (&P)[Shape<C>::SLOTS], double
                     R[sl] = rn;
                 }
         }
-        trP = trP - b / a;
+        if constexpr (DQ) {
+            trP = trP - b / a;
 #pragma unroll
-        for (int sl = 0; sl < SLOTS; sl++)
-            if (act[sl]) {
-                double s1 = fma(ba2 * uc[sl], ur[sl], Q[sl]);
-                double s2 = fma(ia * uc[sl], vr[sl], 0.0); s2 = fma(ia * vc[sl], ur[sl], s2);
-                double qn = s1 + s2;
-                double pn = fma(ia * uc[sl], ur[sl], P[sl]);
-                if (own.r[sl] == i && own.c[sl] == i) { qn = dmaxf(qn, PG_MINV); pn = dmaxf(pn, PG_MINV); }
-                Q[sl] = qn; P[sl] = pn;
-            }
+            for (int sl = 0; sl < SLOTS; sl++)
+                if (act[sl]) {
+                    double s1 = fma(ba2 * uc[sl], ur[sl], Q[sl]);
+                    double s2 = fma(ia * uc[sl], vr[sl], 0.0); s2 = fma(ia * vc[sl], ur[sl], s2);
+                    double qn = s1 + s2;
+                    double pn = fma(ia * uc[sl], ur[sl], P[sl]);
+                    if (own.r[sl] == i && own.c[sl] == i) { qn = dmaxf(qn, PG_MINV); pn = dmaxf(pn, PG_MINV); }
+                    Q[sl] = qn; P[sl] = pn;
+                }
+        } else {
+#pragma unroll
+            for (int sl = 0; sl < SLOTS; sl++)
+                if (act[sl]) {
+                    double pn = fma(ia * uc[sl], ur[sl], P[sl]);
+                    if (own.r[sl] == i && own.c[sl] == i) pn = dmaxf(pn, PG_MINV);
+                    P[sl] = pn;
+                }
+        }
         if (i == M - 2) { o.Pxx_c = (float)gather<SLOTS>(P, tri(M - 2, M - 2)); o.Pyx_c = (float)gather<SLOTS>(P, tri(M - 1, M - 2)); }
     }
     // logdet_Wt_H_inv_W (pyx:957/1029): f32 accumulator += log(pivot), pivots in order; the M-1 logs are taken
@@ -444,9 +482,9 @@ __device__ __forceinline__ void lane_sweeps(double (&P)[Shape<C>::SLOTS], double
     float ld = 0.0f;
     for (int q = 0; q < M - 1; q++) ld = (float)((double)ld + __shfl(lg, q, 64));
     o.yPy = (float)gather<SLOTS>(P, NP - 1);
-    o.yPPy = (float)gather<SLOTS>(Q, NP - 1);
+    o.yPPy = DQ ? (float)gather<SLOTS>(Q, NP - 1) : 0.0f;
     o.yPPPy = FULL ? (float)gather<SLOTS>(R, NP - 1) : 0.0f;
-    o.trP = (float)trP;
+    o.trP = DQ ? (float)trP : 0.0f;
     o.trPP = FULL ? (float)trPP : 0.0f;
     o.ld = ld;
     o.sh = (float)t1;
@@ -612,31 +650,42 @@ __device__ __forceinline__ void slot_passes(const AssocParams &pr, typename EL::
     if constexpr (SL + 1 < Shape<C>::SLOTS) slot_passes<C, PW, HASX, SL + 1, EL>(pr, xrow, lam, lane, htab_out, X, tsum);
 }
 
-// Level-0 Grams at an arbitrary lambda, then the sweeps.
-template <int C, bool FULL, class EL = WaldElem<C>>
+// Level-0 Grams of the powers in MASK at an arbitrary lambda, as they leave the reduce-scatter: P and t1, Q, R and t2.  Which
+// powers share a pass over n follows Shape<C>; every entry is its own fma chain, so its bits do not depend on that grouping.
+template <int C, int MASK, class EL = WaldElem<C>>
+__device__ __forceinline__ void gram_powers(const AssocParams &pr, typename EL::Row xrow, float lam, int lane,
+                                            double (&P)[Shape<C>::SLOTS], double (&Q)[Shape<C>::SLOTS], double (&R)[Shape<C>::SLOTS],
+                                            double &t1, double &t2)
+{
+    constexpr bool DP = (MASK & 1) != 0, DQ = (MASK & 2) != 0, DR = (MASK & 4) != 0;
+    if constexpr (Shape<C>::CHUNKED) {
+        double tq = 0.0;
+        if constexpr (DP) slot_passes<C, 1, true, 0, EL>(pr, xrow, lam, lane, nullptr, P, t1);
+        if constexpr (DQ) slot_passes<C, 2, true, 0, EL>(pr, xrow, lam, lane, nullptr, Q, tq);
+        if constexpr (DR) slot_passes<C, 3, true, 0, EL>(pr, xrow, lam, lane, nullptr, R, t2);
+    } else if constexpr (MASK == PW_PQR && Shape<C>::FUSE_PQR) {
+        gram_pass<C, 7, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+    } else if constexpr (DP && DQ && Shape<C>::FUSE_PQ) {
+        gram_pass<C, 3, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+        if constexpr (DR) gram_pass<C, 4, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+    } else {
+        if constexpr (DP) gram_pass<C, 1, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+        if constexpr (DQ) gram_pass<C, 2, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+        if constexpr (DR) gram_pass<C, 4, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
+    }
+}
+
+// Level-0 Grams at an arbitrary lambda, then the sweeps, for the powers PW (PW_P, PW_PQ or PW_PQR).
+template <int C, int PW, class EL = WaldElem<C>>
 __device__ __forceinline__ void eval_specific(const AssocParams &pr, typename EL::Row xrow, float lam, int lane, const Own<C> &own, EvalOut &o,
                                               double *piv)
 {
     constexpr int SLOTS = Shape<C>::SLOTS;
     double P[SLOTS], Q[SLOTS], R[SLOTS], t1 = 0.0, t2 = 0.0;
 #pragma unroll
-    for (int sl = 0; sl < SLOTS; sl++) R[sl] = 0.0;
-    if constexpr (Shape<C>::CHUNKED) {
-        double tq = 0.0;
-        slot_passes<C, 1, true, 0, EL>(pr, xrow, lam, lane, nullptr, P, t1);
-        slot_passes<C, 2, true, 0, EL>(pr, xrow, lam, lane, nullptr, Q, tq);
-        if (FULL) slot_passes<C, 3, true, 0, EL>(pr, xrow, lam, lane, nullptr, R, t2);
-    } else if constexpr (FULL && Shape<C>::FUSE_PQR) {
-        gram_pass<C, 7, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
-    } else if constexpr (Shape<C>::FUSE_PQ) {
-        gram_pass<C, 3, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
-        if (FULL) gram_pass<C, 4, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
-    } else {
-        gram_pass<C, 1, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
-        gram_pass<C, 2, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
-        if (FULL) gram_pass<C, 4, true, EL>(pr, xrow, lam, lane, nullptr, P, Q, R, t1, t2);
-    }
-    lane_sweeps<C, FULL>(P, Q, R, own, t1, t2, lane, o, piv);
+    for (int sl = 0; sl < SLOTS; sl++) { Q[sl] = 0.0; R[sl] = 0.0; }
+    gram_powers<C, PW, EL>(pr, xrow, lam, lane, P, Q, R, t1, t2);
+    lane_sweeps<C, PW>(P, Q, R, own, t1, t2, lane, o, piv);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -922,8 +971,8 @@ template <int C, bool LRT, bool PHENO = false>
 // PHENO (pg_assoc_pheno_dev; never with LRT): the decade scan's x-entries are read from pr.xbuf; one launch per phenotype, so that
 // every (SNP, phenotype) is one wavefront and a workgroup holds WPB of them, as in a single-phenotype launch.
 // two waves per SIMD for EVERY c (PG_WAVES = 2): a lone wave cannot issue fp64 VALU at the pipe's rate (measured 2.3x faster at 2 than at
-// 1).  From c = 4 on the instantiations are capped at 256 VGPRs with spills to scratch (c = 5: 58 VGPR + 35 SGPR spills, 196 B; c = 10:
-// 107, 320 B; c = 14: 276 B) — all of them in the per-evaluation outer loops; the Gram loops themselves are scratch-free (checked on the
+// 1).  From c = 4 on the instantiations are capped at 256 VGPRs with spills to scratch (c = 5: 81 VGPR + 40 SGPR spills, 208 B; c = 10:
+// 121, 356 B; c = 14: 572 B) — all of them in the per-evaluation outer loops; the Gram loops themselves are scratch-free (checked on the
 // shipped code object: VERDICT r3)
 __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams pr)
 {
@@ -933,11 +982,14 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
     static_assert(!(PHENO && LRT), "the multi-phenotype search has no LRT");
     const long long g = (long long)blockIdx.x * WPB + wave;
     if (g >= pr.p) return;  // whole wavefront leaves; no workgroup barrier is used anywhere in this kernel
-    // per-wave LDS: xent[NLAM][2M] doubles | evs[NLAM] | d1s[NLAM] | lls[NLAM] | vals[n_vals]
+    // per-wave LDS: [piv] | [sav] | xent[NLAM][2M] doubles | evs[NLAM] | d1s[NLAM] | lls[NLAM] | vals[n_vals]
     constexpr size_t piv_bytes = Shape<C>::SWEEP_LDS ? (size_t)3 * M * 8 : 0;
-    unsigned char *base = smem + (size_t)wave * assoc_per_wave_bytes(M, Shape<C>::SWEEP_LDS, sizeof(EvalOut), pr.n_vals);
+    constexpr bool REUSE = Shape<C>::NEWTON_REUSE;
+    unsigned char *base = smem + (size_t)wave * assoc_per_wave_bytes(M, Shape<C>::SWEEP_LDS, Shape<C>::SAV_SLOTS, sizeof(EvalOut), pr.n_vals);
     double *piv = reinterpret_cast<double *>(base);          // pivot column exchange of the sweeps (c >= 14 only)
     base += piv_bytes;
+    double *sav = reinterpret_cast<double *>(base) + lane;   // Brent's last two evaluations: this lane's P[SLOTS], Q[SLOTS], t1, 64 doubles apart
+    base += assoc_sav_doubles(Shape<C>::SAV_SLOTS) * 8;
     double *xent = reinterpret_cast<double *>(base);
     EvalOut *evs = reinterpret_cast<EvalOut *>(base + (size_t)NLAM * 2 * M * 8);
     float *d1s = reinterpret_cast<float *>(evs + NLAM);
@@ -972,7 +1024,7 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
             R[sl] = 0.0;
         }
         EvalOut e;
-        lane_sweeps<C, false>(P, Q, R, own, pr.t1tab[t], 0.0, lane, e, piv);
+        lane_sweeps<C, PW_PQ>(P, Q, R, own, pr.t1tab[t], 0.0, lane, e, piv);
         if (lane == 0) {
             evs[t] = e;
             d1s[t] = d1_f(pr, pr.lam11[t], e.yPy, e.yPPy, e.trP);
@@ -985,7 +1037,10 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
     EvalOut best_e;
     if (best_l < lls[NLAM - 1]) { best_l = lls[NLAM - 1]; best_lambda = pr.lam11[NLAM - 1]; best_e = evs[NLAM - 1]; }
     else { best_lambda = pr.lam11[0]; best_e = evs[0]; }
-    unsigned n_fast = 0, n_full = 0;
+    // n_fast / n_full count evaluations (two-power | three-power quadratic forms asked for), whatever passes they took; n_ponly:
+    // evaluations that made P alone, n_reuse: Newton evaluations that made R alone on Brent's P and Q
+    unsigned n_fast = 0, n_full = 0, n_ponly = 0, n_reuse = 0;
+    constexpr int PW_FINAL = PG_ASSOC_FINAL_P ? PW_P : PW_PQ;   // at the root only yPy, ld, Pxx_c and Pyx_c are read
     if (pr.grid) {
         for (int t = 0; t < NLAM - 1; t++)   // pyx:119-130, k = -5..4, strict '>'
             if (lls[t] > best_l) { best_l = lls[t]; best_lambda = pr.lam11[t]; best_e = evs[t]; }
@@ -994,23 +1049,63 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
             const float f0 = d1s[k], f1 = d1s[k + 1];
             if (__builtin_signbit(f0) == __builtin_signbit(f1)) continue;   // copysignf product < 0 (pyx:174)
             const float l0 = pr.lam11[k], l1 = pr.lam11[k + 1];
+            // Brent returns one of the lambdas it evaluated, mostly one of the last two (not always the last: the bracket's other
+            // end when that has the smaller |f|), and Newton starts there: the level-0 P, Q and t1 of Brent's last two evaluations
+            // are kept as they leave the reduce-scatter (the sweeps overwrite them), this lane's entries in the wave's LDS.
+            float sav_lam0 = NAN, sav_lam1 = NAN;
+            unsigned sav_next = 0;
             double root = brentq_dev(
                 [&](double x) -> double {
                     EvalOut e;
                     const float lf = (float)x;      // pyx:1631: np.float32_t lam
-                    eval_specific<C, false>(pr, xrow, lf, lane, own, e, piv);
+                    if constexpr (REUSE) {
+                        double P[SLOTS], Q[SLOTS], R[SLOTS], t1 = 0.0, t2 = 0.0;
+#pragma unroll
+                        for (int sl = 0; sl < SLOTS; sl++) R[sl] = 0.0;
+                        gram_powers<C, PW_PQ>(pr, xrow, lf, lane, P, Q, R, t1, t2);
+                        double *sv = sav + sav_next * Shape<C>::SAV_STRIDE;
+#pragma unroll
+                        for (int sl = 0; sl < SLOTS; sl++) { sv[64 * sl] = P[sl]; sv[64 * (SLOTS + sl)] = Q[sl]; }
+                        sv[64 * 2 * SLOTS] = t1;
+                        if (sav_next) sav_lam1 = lf; else sav_lam0 = lf;
+                        sav_next ^= 1u;
+                        lane_sweeps<C, PW_PQ>(P, Q, R, own, t1, t2, lane, e, piv);
+                    } else {
+                        eval_specific<C, PW_PQ>(pr, xrow, lf, lane, own, e, piv);
+                    }
                     n_fast++;
                     return (double)d1_f(pr, lf, e.yPy, e.yPPy, e.trP);
                 },
                 (double)l0, (double)l1, (double)f0, (double)f1);
-            // newton (pyx:1349-1416), all f32
+            // newton (pyx:1349-1416), all f32.  Its first evaluation, at a lambda bit-equal to a kept one, needs only the R pass;
+            // anything else (a decade endpoint, an older Brent point, NaN) and every later evaluation takes all three powers.
+            bool first = true;
             const float lroot = newton_dev(pr, (float)root, l0, l1, [&](float lf, EvalOut &e) {
-                eval_specific<C, true>(pr, xrow, lf, lane, own, e, piv);
+                if constexpr (REUSE) {
+                    const unsigned lb = __float_as_uint(lf);
+                    const int hit = !(first && lf == lf) ? -1 : (lb == __float_as_uint(sav_lam0)) ? 0 : (lb == __float_as_uint(sav_lam1)) ? 1 : -1;
+                    first = false;
+                    double P[SLOTS], Q[SLOTS], R[SLOTS], t1 = 0.0, t2 = 0.0;
+                    if (hit >= 0) {
+                        const double *sv = sav + hit * Shape<C>::SAV_STRIDE;
+#pragma unroll
+                        for (int sl = 0; sl < SLOTS; sl++) { P[sl] = sv[64 * sl]; Q[sl] = sv[64 * (SLOTS + sl)]; }
+                        t1 = sv[64 * 2 * SLOTS];
+                        gram_powers<C, PW_R>(pr, xrow, lf, lane, P, Q, R, t1, t2);
+                        n_reuse++;
+                    } else {
+                        gram_powers<C, PW_PQR>(pr, xrow, lf, lane, P, Q, R, t1, t2);
+                    }
+                    lane_sweeps<C, PW_PQR>(P, Q, R, own, t1, t2, lane, e, piv);
+                } else {
+                    eval_specific<C, PW_PQR>(pr, xrow, lf, lane, own, e, piv);
+                }
                 n_full++;
             });
             EvalOut e;
-            eval_specific<C, false>(pr, xrow, lroot, lane, own, e, piv);   // pyx:186
+            eval_specific<C, PW_FINAL>(pr, xrow, lroot, lane, own, e, piv);   // pyx:186
             n_fast++;
+            if (PW_FINAL == PW_P) n_ponly++;
             const float ldH = device_logdet_H(pr, lroot, lane, vals);
             const float ll = logl_f(pr, e.yPy, ldH, e.ld);       // pyx:188
             if (ll > best_l) { best_l = ll; best_lambda = lroot; best_e = e; }
@@ -1036,7 +1131,7 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
                 [&](double x) -> double {
                     EvalOut e;
                     const float lf = (float)x;
-                    eval_specific<C, false>(pr, xrow, lf, lane, own, e, piv);
+                    eval_specific<C, PW_PQ>(pr, xrow, lf, lane, own, e, piv);
                     n_fast++;
                     return (double)ml_d1_f(pr, lf, e.yPy, e.yPPy, e.sh);
                 },
@@ -1045,7 +1140,7 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
             for (int itr = 0; itr < 10; itr++) {
                 EvalOut e;
                 const float lf = (float)p0;
-                eval_specific<C, true>(pr, xrow, lf, lane, own, e, piv);
+                eval_specific<C, PW_PQR>(pr, xrow, lf, lane, own, e, piv);
                 n_full++;
                 const float fval = ml_d1_f(pr, lf, e.yPy, e.yPPy, e.sh);
                 if (fval == 0.0f) { pn = p0; break; }
@@ -1058,8 +1153,9 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
             if (ml_l == ml_l) {
                 EvalOut e;
                 const float lf = (float)pn;
-                eval_specific<C, false>(pr, xrow, lf, lane, own, e, piv);
+                eval_specific<C, PW_FINAL>(pr, xrow, lf, lane, own, e, piv);   // the ML logL reads yPy only
                 n_fast++;
+                if (PW_FINAL == PW_P) n_ponly++;
                 const float l = ml_logl_f(pr, e.yPy, device_logdet_H(pr, lf, lane, vals));
                 if (l != l || l > ml_l) { ml_l = l; ml_lam = lf; }
             }
@@ -1076,6 +1172,11 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
         pr.beta[g] = b; pr.se[g] = sb; pr.tau[g] = ta; pr.lam[g] = best_lambda; pr.F[g] = t * t;
         if (pr.stats) { atomicAdd(&pr.stats[0], (unsigned long long)n_fast); atomicAdd(&pr.stats[1], (unsigned long long)n_full); }
         if (pr.trace) pr.trace[g] = n_fast | (n_full << 16);
+        if (pr.passes) {   // every evaluation passes over n once per power it makes: all make P but the reusing ones, all Q but those and the P-only ones
+            const unsigned long long np = (unsigned long long)(n_fast + n_full - n_reuse);
+            atomicAdd(&pr.passes[0], np); atomicAdd(&pr.passes[1], np - n_ponly);
+            atomicAdd(&pr.passes[2], (unsigned long long)n_full); atomicAdd(&pr.passes[3], (unsigned long long)n_reuse);
+        }
     }
 }
 
@@ -1262,7 +1363,7 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_gxe_kernel(AssocPara
             R[sl] = 0.0;
         }
         EvalOut e;
-        lane_sweeps<C, false>(P, Q, R, own, pr.t1tab[t], 0.0, lane, e, piv);
+        lane_sweeps<C, PW_PQ>(P, Q, R, own, pr.t1tab[t], 0.0, lane, e, piv);
         if (lane == 0) {
             evs[t] = e;
             d1s[t] = d1_f(pr, pr.lam11[t], e.yPy, e.yPPy, e.trP);
@@ -1284,17 +1385,17 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_gxe_kernel(AssocPara
             [&](double x) -> double {
                 EvalOut e;
                 const float lf = (float)x;
-                eval_specific<C, false, EL>(pr, xr, lf, lane, own, e, piv);
+                eval_specific<C, PW_PQ, EL>(pr, xr, lf, lane, own, e, piv);
                 n_fast++;
                 return (double)d1_f(pr, lf, e.yPy, e.yPPy, e.trP);
             },
             (double)l0, (double)l1, (double)f0, (double)f1);
         const float lroot = newton_dev(pr, (float)root, l0, l1, [&](float lf, EvalOut &e) {
-            eval_specific<C, true, EL>(pr, xr, lf, lane, own, e, piv);
+            eval_specific<C, PW_PQR, EL>(pr, xr, lf, lane, own, e, piv);
             n_full++;
         });
         EvalOut e;
-        eval_specific<C, false, EL>(pr, xr, lroot, lane, own, e, piv);
+        eval_specific<C, PW_PQ, EL>(pr, xr, lroot, lane, own, e, piv);
         n_fast++;
         const float ldH = device_logdet_H(pr, lroot, lane, vals);
         const float ll = logl_f(pr, e.yPy, ldH, e.ld);
@@ -1336,7 +1437,7 @@ static int launch_assoc(pg_ctx *ctx, AssocParams &pr)
 {
     // launch size from the instantiation's own Shape (the same constexpr the kernel indexes with), checked on the host
     // against the device limit before anything is launched
-    const size_t lds = (size_t)WPB * assoc_per_wave_bytes(Shape<C>::M, Shape<C>::SWEEP_LDS, sizeof(EvalOut), pr.n_vals);
+    const size_t lds = (size_t)WPB * assoc_per_wave_bytes(Shape<C>::M, Shape<C>::SWEEP_LDS, Shape<C>::SAV_SLOTS, sizeof(EvalOut), pr.n_vals);
     static_assert(Shape<C>::M == C + 2, "Shape<C>::M");
     PG_REQUIRE(pr.n_vals >= 0 && lds <= 160 * 1024, "assoc: c = %d, n_vals = %d need %zu bytes of LDS per workgroup", C, pr.n_vals, lds);
     setup_tabs_kernel<C><<<NLAM, 64, (size_t)pr.n_vals * 4 + 16, ctx->stream>>>(pr);
@@ -1374,7 +1475,7 @@ static int launch_pheno(pg_ctx *ctx, AssocParams &pr, const PhenoLaunch &pl)
             default: set_error("assoc_pheno: chunk width %d", pl.tpad); return PG_EINVAL;
         }
     } else {
-        const size_t lds = (size_t)WPB * assoc_per_wave_bytes(Shape<C>::M, Shape<C>::SWEEP_LDS, sizeof(EvalOut), pr.n_vals);
+        const size_t lds = (size_t)WPB * assoc_per_wave_bytes(Shape<C>::M, Shape<C>::SWEEP_LDS, Shape<C>::SAV_SLOTS, sizeof(EvalOut), pr.n_vals);
         PG_REQUIRE(pr.n_vals >= 0 && lds <= 160 * 1024, "assoc_pheno: c = %d, n_vals = %d need %zu bytes of LDS per workgroup", C, pr.n_vals, lds);
         if (lds > 64 * 1024)
             PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&assoc_kernel<C, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1844,6 +1945,7 @@ static int assoc_run(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, c
     pr.beta = beta; pr.se = se; pr.tau = tau; pr.lam = lambda; pr.F = F;
     pr.stats = stats_dev;
     pr.trace = lrt ? nullptr : ctx->eval_trace;
+    pr.passes = lrt ? nullptr : ctx->pass_stats;
 
     build_fixed_kernel<<<(pr.npad + 255) / 256, 256, 0, ctx->stream>>>(pr.n, pr.npad, c, (int)ldw, pr.rowf, d, Wr, yr, (float *)ctx->fixed);
     PG_HIP(hipGetLastError());
@@ -1898,6 +2000,16 @@ extern "C" int pg_assoc_set_eval_trace(pg_ctx *ctx, unsigned *trace_dev)
 {
     PG_REQUIRE(ctx, "pg_assoc_set_eval_trace: NULL ctx");
     ctx->eval_trace = trace_dev;
+    return PG_OK;
+}
+
+// Which Gram passes ran: the next pg_assoc_dev calls of this context add, over their SNPs, the passes over n that produced P, Q
+// and R (a fused pass counts once for each power it produces; the decade scan is not counted) and the Newton starts that reused
+// Brent's P and Q to dev4[0..3]; NULL switches it off.
+extern "C" int pg_assoc_set_pass_stats(pg_ctx *ctx, unsigned long long *dev4)
+{
+    PG_REQUIRE(ctx, "pg_assoc_set_pass_stats: NULL ctx");
+    ctx->pass_stats = dev4;
     return PG_OK;
 }
 

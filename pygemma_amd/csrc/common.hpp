@@ -52,6 +52,7 @@ struct pg_ctx {
     void *tabs = nullptr;  size_t tabs_bytes = 0;    // htab + fixed grams + ldH + t1
     unsigned long long *stats = nullptr;
     unsigned *eval_trace = nullptr;                  // caller-owned (pg_assoc_set_eval_trace)
+    unsigned long long *pass_stats = nullptr;        // caller-owned (pg_assoc_set_pass_stats)
     pg::NpSumPlan plan;
     void *pheno = nullptr; size_t pheno_bytes = 0;   // pg_assoc_pheno_dev: per-phenotype tables + the shared scan buffer
     void *score = nullptr; size_t score_bytes = 0;   // pg_score_dev: the fixed vectors h, B, P0 y and P_yy

@@ -23,12 +23,21 @@ def assoc(d, Wr, yr, Xr, grid=False, ctx=None, want_p=True, return_stats=False):
         F, pv = np.empty(p, np.float64), np.empty(p, np.float64)
         stats = np.zeros(2, np.uint64)
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        _lib.check(L.pg_assoc(ctx.handle, n, c, p, vp(d), vp(Wr), vp(yr), vp(Xr), int(bool(grid)), vp(beta), vp(se),
-                              vp(tau), vp(lam), vp(F), vp(pv) if want_p else None, vp(stats)), "pg_assoc")
+        dpass = ctx.to_device(np.zeros(4, np.uint64)) if return_stats else None
+        if return_stats:
+            _lib.check(L.pg_assoc_set_pass_stats(ctx.handle, dpass.ptr), "pg_assoc_set_pass_stats")
+        try:
+            _lib.check(L.pg_assoc(ctx.handle, n, c, p, vp(d), vp(Wr), vp(yr), vp(Xr), int(bool(grid)), vp(beta), vp(se),
+                                  vp(tau), vp(lam), vp(F), vp(pv) if want_p else None, vp(stats)), "pg_assoc")
+        finally:
+            if return_stats:
+                L.pg_assoc_set_pass_stats(ctx.handle, None)
         out = {"beta": beta, "se_beta": se, "tau": tau, "lambda": lam.astype(np.float64), "F_wald": F,
                "p_wald": pv if want_p else None}
         if return_stats:
             out["n_evals"] = stats.astype(np.int64)
+            # passes over n that produced P, Q, R (a fused pass counts once per power) and Newton starts on Brent's P and Q
+            out["passes"] = dpass.download((4,), np.uint64).astype(np.int64)
         return out
 
 
