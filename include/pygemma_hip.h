@@ -185,6 +185,33 @@ int pg_score_null_dev(pg_ctx *ctx, int64_t n, int c, const float *d, const float
 int pg_score_dev(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, const float *Wr, const float *yr, float lambda0,
                  const float *Xr, int64_t ldx, float *beta, float *se, float *tau, float *lambda, double *F, double *pval);
 
+/* ---- The plain linear model (GEMMA's -lm 1; the per-SNP OLS loop of experiments/1000G/run_lin_reg.py): the K-free baseline a
+ * mixed-model scan is read against, straight from RAW genotypes — no eigensolver, no rotation (csrc/lm.hip).  For phenotype k
+ * (k < t), SNP x and covariates W (n x c, full rank):  y_k = W alpha + x beta + eps,  df = n - c - 1.
+ *   pg_lm_work_bytes : bytes of the device work area for (n, c, t); 0 for a shape the entries refuse
+ *   pg_lm_setup_dev  : once per (W, Y), all in fp64: W'W = L L' (Cholesky), Q = W L^-T, Y~ = Y - Q Q'Y, syy_k = y~_k'y~_k; the panel
+ *                      [Q | Y~] (columns padded to a multiple of 16) goes into work.  W n x c row-major, Y phenotype-major
+ *                      (phenotype k is Y[k ldy .. k ldy + n), ldy >= n), float32 each.
+ *   pg_lm_x_dev      : pb SNPs of an (n x pb) sample-major (snp_major = 0, row stride ldX >= pb) or (pb x n) SNP-major (ldX >= n)
+ *                      block of dtype PG_DTYPE_*; values as the reference's X.astype(np.float32) (float64 rounded per element).
+ *   pg_lm_bed_dev    : pb packed .bed records (row stride ldb >= ceil(n/4) bytes), code convention and count_a1 of
+ *                      pg_rotate_bed_dev; a missing call takes the fp64 mean of the called genotypes of its SNP rounded to float32.
+ *                      Per SNP, fp64 on v_mfma_f64_16x16x4_f64:  sxx = x'x - |Q'x|^2,  sxy_k = x'y~_k,  rss_k = syy_k - sxy_k^2 / sxx;
+ *                      beta = sxy / sxx, se = sqrt(rss / (df sxx)), tau = df / rss (float32 each), F = df sxy^2 / (sxx rss),
+ *                      pval = F(1, df).sf(F) (float64; pval may be NULL).  There is no lambda.
+ *                      Outputs are phenotype-major windows: phenotype k's SNP g at [k ldo + g], ldo >= pb.
+ *                      A SNP with sxx <= 1e-10 x'x (constant, in span(W)), a NaN or Inf, or an all-missing .bed record gets NaN in all
+ *                      five columns for every phenotype; a rank-deficient or non-finite W (the Cholesky fails) gives NaN everywhere; a
+ *                      non-finite phenotype NaN in its own rows only.  A row depends only on its SNP and on (W, Y).
+ * PG_ENOTSUP for c outside 1..PG_MAX_COVARIATES or c + t > 64; PG_EINVAL for NULL pointers (but pval), t < 1, n - c - 1 <= 0 or strides
+ * too small: a refused call enqueues nothing. */
+size_t pg_lm_work_bytes(int64_t n, int c, int t);
+int pg_lm_setup_dev(pg_ctx *ctx, int64_t n, int c, int t, const float *W, const float *Y, int64_t ldy, void *work);
+int pg_lm_x_dev(pg_ctx *ctx, int64_t n, int c, int t, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, const void *work,
+                float *beta, float *se, float *tau, double *F, double *pval, int64_t ldo);
+int pg_lm_bed_dev(pg_ctx *ctx, int64_t n, int c, int t, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, const void *work,
+                  float *beta, float *se, float *tau, double *F, double *pval, int64_t ldo);
+
 /* ---- SNP-by-environment interaction (GEMMA's -gxe): for SNP g with rotated genotype x = U'x_g and rotated interaction
  * xe = U'(x_g o e), the REML Wald test of xe in  y ~ W' + x + xe,  W' = the c shared covariates (the caller's W and U'e).
  * Row g is by definition calculate(d, yr, [W', x], xe) of pg_assoc_dev's arithmetic with c + 1 covariates (decade scan,

@@ -38,7 +38,7 @@ from .bed import PackedBed
 from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_restricted, newton, the *_overload scalars)
 from . import model as _model
 
-__all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "SampleIter", "pinned_empty", "pin", "kinship"] + _model.__all__
+__all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "SampleIter", "pinned_empty", "pin", "kinship"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -679,6 +679,190 @@ def _kinship_stream(G, standardize, device, snp_batch):
             for ev in events:
                 L.pg_event_destroy(up.handle, ev)
             stg.close()
+
+
+_LM_COLS = ("beta", "se_beta", "tau", "F_wald", "p_wald")
+_LM_SLOT_BYTES = 256 << 20     # device bytes of one upload slot by default, and SNPs per batch at most: many batches, so that only the
+_LM_BATCH = 16384              # first upload (and, from pageable memory, the first staging copy) is exposed
+_CHI2_MEDIAN = 0.4549364       # chi2.ppf(0.5, 1)
+
+
+def _lm_columns(Y):
+    """(labels, float32 (t, n) phenotype-major matrix) of pygemma_lm's Y: (n,), (n, 1), (n, t) or a DataFrame, cast per column as
+    pygemma_multi casts it."""
+    if isinstance(Y, pd.DataFrame):
+        labels = list(Y.columns)
+        cols = [np.asarray(Y.iloc[:, k]) for k in range(Y.shape[1])]
+    else:
+        Ya = np.asarray(Y)
+        if Ya.ndim == 1:
+            Ya = Ya.reshape(-1, 1)
+        if Ya.ndim != 2:
+            raise ValueError(f"Y must be (n,), (n, 1) or (n, t), got shape {Ya.shape}")
+        labels = list(range(Ya.shape[1]))
+        cols = [Ya[:, k] for k in range(Ya.shape[1])]
+    if not cols:
+        raise ValueError("Y has no phenotype columns")
+    Yt = np.empty((len(cols), cols[0].shape[0]), np.float32)
+    for k, col in enumerate(cols):
+        Yt[k] = col.astype(np.float32)                       # lmm.py:115-116, per column
+    return labels, Yt
+
+
+def pygemma_lm(Y, X, W, snps=None, verbose=0, device=0, snp_batch=None, stats=None):
+    """The plain linear model per SNP (GEMMA's -lm 1; the OLS loop of experiments/1000G/run_lin_reg.py): y_k = W alpha + x_g beta + eps,
+    the K-free baseline a mixed-model scan is read against (how much inflation does K remove?).  Neither eigensolver nor rotation:
+    the scan reads the raw genotypes once, so a whole-genome pass costs little more than moving X.
+
+    Y: (n,), (n, 1), (n, t) or a DataFrame, cast per column to float32 like pygemma_multi's; W (n, c), c = 1..30 (bring your own
+    intercept), c + t <= 64; X (n, p): whatever lmm.kinship's streamed path takes — a PackedBed, or an int8, uint8, float32 or float64
+    array in C or Fortran order, pinned or pageable — read where it lies, without a host copy or cast of the whole matrix.  Values
+    are the reference's X.astype(np.float32); a missing .bed call takes the mean of the called genotypes of its SNP
+    (PackedBed.to_float(impute=True)).
+    In fp64 (csrc/lm.hip), with Q an orthonormal basis of span(W), y~ = y - Q Q'y and df = n - c - 1:
+      sxx = x'x - |Q'x|^2, sxy = x'y~, rss = y~'y~ - sxy^2/sxx
+      beta = sxy/sxx, se_beta = sqrt(rss/(df sxx)), tau = df/rss     (float32)
+      F_wald = df sxy^2/(sxx rss), p_wald = F(1, df).sf(F_wald)      (float64)
+    One phenotype returns the DataFrame beta, se_beta, tau, F_wald, p_wald[, SNPs] (no lambda column); several return a dict in
+    column order {label: frame}, keyed like pygemma_multi's, each frame bit-identical to the one-column call.  A SNP that is constant
+    or in span(W) (sxx <= 1e-10 x'x), holds a NaN/Inf or is an all-missing .bed record gets NaN rows for every phenotype; a
+    rank-deficient or non-finite W gives NaN everywhere; a non-finite phenotype NaN in its own frame only.
+    SNP batches of `snp_batch` columns (default: from n and the free device memory) are uploaded on a second stream into two device
+    slots, one batch ahead of the kernels; the results stay on the device until one download at the end, and do not depend on the
+    batch boundaries.  `stats` receives batches, bytes_in, seconds and lambda_gc — per phenotype, median(chi2.isf(p_wald, 1)) /
+    chi2.ppf(0.5, 1) over the non-NaN rows, as run_lin_reg.py computes it.  Refused with ValueError before any device work: shape
+    mismatches, X not 2-D or of another dtype, W with other than 1..30 columns, c + t > 64, n - c - 1 <= 0, a bad snp_batch."""
+    if snp_batch is not None and (isinstance(snp_batch, bool) or not isinstance(snp_batch, (int, np.integer)) or snp_batch < 1):
+        raise ValueError(f"snp_batch must be a positive integer, not {snp_batch!r}")
+    packed = isinstance(X, PackedBed)
+    if not packed:
+        X = np.asarray(X)
+        if X.ndim != 2:
+            raise ValueError(f"X must be a 2-D (n, p) array, not {X.ndim}-D")
+        if X.dtype not in _KIN_DTYPES:
+            raise ValueError(f"pygemma_lm takes int8, uint8, float32 or float64 genotypes (or a PackedBed), not {X.dtype}")
+        if not (X.flags.c_contiguous or X.flags.f_contiguous):
+            X = np.ascontiguousarray(X)
+    n, p = X.shape
+    W = np.asarray(W)
+    if W.ndim != 2 or not 1 <= W.shape[1] <= 30:
+        raise ValueError(f"the linear model takes W with 1 to 30 columns, got W {W.shape}")
+    labels, Yt = _lm_columns(Y)
+    t, c = len(labels), W.shape[1]
+    if W.shape[0] != n or Yt.shape[1] != n:
+        raise ValueError(f"shape mismatch: Y has {Yt.shape[1]} rows, X {n}, W {W.shape[0]}")
+    if c + t > 64:
+        raise ValueError(f"the linear model takes c + t <= 64 panel columns, got c = {c}, t = {t}")
+    if n - c - 1 <= 0:
+        raise ValueError(f"the linear model needs n - c - 1 > 0 (n = {n}, c = {c})")
+    if snps is not None and len(snps) != p:
+        raise ValueError(f"shape mismatch: {len(snps)} SNP names for {p} SNPs")
+    W = np.ascontiguousarray(W.astype(np.float32))           # lmm.py:118-119
+    out = _lm_stream(X, W, Yt, device, snp_batch, verbose, stats)
+    frames = {}
+    for k, lab in enumerate(labels):
+        df = pd.DataFrame({col: out[col][k] for col in _LM_COLS}, columns=list(_LM_COLS))
+        if snps is not None:
+            df["SNPs"] = snps
+        frames[lab] = df
+    if stats is not None:
+        from scipy import stats as _sps      # lazily, as model.py does
+        lam = []
+        for k in range(t):
+            pv = out["p_wald"][k]
+            pv = pv[~np.isnan(pv)]
+            lam.append(float(np.median(_sps.chi2.isf(pv, 1)) / _CHI2_MEDIAN) if pv.size else float("nan"))
+        stats["lambda_gc"] = lam
+    return frames[labels[0]] if t == 1 else frames
+
+
+def _lm_stream(X, W, Yt, device, snp_batch, verbose, stats):
+    """The streamed linear-model scan, modelled on _kinship_stream: pg_lm_setup_dev once, then SNP batches through pg_lm_{bed,x}_dev
+    into windows of the (t, p) result arrays on the device.  Uploads run on a second stream into two device slots, one batch ahead
+    of the kernels, ordered by events.  Returns the five (t, p) host arrays."""
+    L = _lib.load()
+    t0 = time.time()
+    packed = isinstance(X, PackedBed)
+    (t, n), c = Yt.shape, W.shape[1]
+    p = X.p if packed else X.shape[1]
+    if packed:
+        src_arr, row_bytes, snp_major, esz = X.data, X.data.shape[1], True, 1
+    else:
+        src_arr, esz = X, X.itemsize
+        snp_major = X.flags.f_contiguous and not X.flags.c_contiguous
+        row_bytes = n * esz
+    direct = _lib.is_pinned(src_arr) and (not packed or src_arr.flags.c_contiguous)
+    if _lib.device_count() < 1:
+        raise _lib.PgError("no MI355X visible: pygemma_amd has no CPU path")
+    with _lib.Context(device) as ctx, _lib.Context(device) as up:
+        free, _total = ctx.mem_info()
+        fixed = int(L.pg_lm_work_bytes(n, c, t)) + 28 * t * max(p, 1) + 4 * n * (c + t)
+
+        def need(pb):
+            return fixed + 2 * pb * row_bytes
+
+        if snp_batch is None:
+            pb = min(max(p, 1), _LM_BATCH, max(128, _LM_SLOT_BYTES // row_bytes // 128 * 128))
+            while pb > 128 and need(pb) > 0.9 * free:
+                pb = max(128, pb // 2)
+        else:
+            pb = min(max(p, 1), int(snp_batch))
+        if need(pb) > free:
+            raise _lib.PgError(f"pygemma_lm: n={n}, p={p}, t={t}, snp_batch={pb} needs {need(pb) / 2**30:.2f} GiB of device memory (panel, "
+                               f"{t} x {p} result rows, two batch slots), {free / 2**30:.2f} GiB free on GPU {device}")
+        dW, dY = ctx.to_device(W), ctx.to_device(Yt)
+        work = ctx.alloc(L.pg_lm_work_bytes(n, c, t))
+        _lib.check(L.pg_lm_setup_dev(ctx.handle, n, c, t, dW.ptr, dY.ptr, n, work.ptr), "pg_lm_setup_dev")
+        res = [ctx.alloc(max(t * p, 1) * (4 if k < 3 else 8)) for k in range(5)]
+        slots = [ctx.alloc(pb * row_bytes) for _ in range(2)]
+        stg = _Pinned(up, *[pb * row_bytes] * (0 if direct else 2))
+        events = []
+        batches = [(s, min(s + pb, p)) for s in range(0, p, pb)]
+        try:
+            for c_ in (up, up, ctx, ctx):
+                ev = C.c_void_p()
+                _lib.check(L.pg_event_create(c_.handle, C.byref(ev)), "pg_event_create")
+                events.append(ev)
+            ev_up, ev_done = events[:2], events[2:]
+
+            def upload(b):
+                s, e = batches[b]
+                k = b % 2
+                if b >= 2:
+                    _lib.check(L.pg_stream_wait_event(up.handle, ev_done[k]), "pg_stream_wait_event")   # batch b-2 is done with the slot
+                    if not direct:
+                        _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")    # the DMA of batch b-2 has left the staging
+                # SNP-major: the records / columns [s, e) back to back; sample-major: the column window of every row at row stride e - s
+                _put_window(up, X, s, e, slots[k].ptr, None if snp_major else (e - s) * esz, None if direct else stg.bufs[k])
+                _lib.check(L.pg_event_record(up.handle, ev_up[k]), "pg_event_record")
+
+            if batches:
+                upload(0)
+            for b, (s, e) in enumerate(batches):
+                k, w = b % 2, e - s
+                _lib.check(L.pg_stream_wait_event(ctx.handle, ev_up[k]), "pg_stream_wait_event")
+                win = [r.ptr + s * (4 if j < 3 else 8) for j, r in enumerate(res)]      # SNPs [s, e) of every phenotype's row: ldo = p
+                if packed:
+                    _lib.check(L.pg_lm_bed_dev(ctx.handle, n, c, t, w, slots[k].ptr, row_bytes, int(X.count_A1), work.ptr, *win, p), "pg_lm_bed_dev")
+                else:
+                    _lib.check(L.pg_lm_x_dev(ctx.handle, n, c, t, w, slots[k].ptr, _KIN_DTYPES[X.dtype], n if snp_major else w, int(snp_major),
+                                             work.ptr, *win, p), "pg_lm_x_dev")
+                _lib.check(L.pg_event_record(ctx.handle, ev_done[k]), "pg_event_record")
+                if b + 1 < len(batches):
+                    upload(b + 1)      # overlaps the kernels of batch b
+                _log(verbose - 1, f"linear model: SNPs [{s},{e}) queued")
+            ctx.sync()
+            out = {col: r.download((t, p), np.float32 if j < 3 else np.float64) for j, (col, r) in enumerate(zip(_LM_COLS, res))}
+        finally:
+            up.sync()
+            ctx.sync()
+            for ev in events:
+                L.pg_event_destroy(up.handle, ev)
+            stg.close()
+    if stats is not None:
+        stats.update({"batches": len(batches), "bytes_in": p * row_bytes, "seconds": time.time() - t0})
+    _log(verbose, f"Linear model: {p} SNPs x {t} phenotype(s) with {n} individuals in {time.time() - t0:.3f} s")
+    return out
 
 
 def _zkzt(L, Z, K):

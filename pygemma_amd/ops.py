@@ -74,6 +74,50 @@ def score(d, Wr, yr, Xr, lam0=None, ctx=None):
         return res
 
 
+_LM_DTYPES = {np.dtype(np.int8): 0, np.dtype(np.uint8): 1, np.dtype(np.float32): 2, np.dtype(np.float64): 3}   # PG_DTYPE_*
+LM_COLS = ("beta", "se_beta", "tau", "F_wald", "p_wald")
+
+
+def lm(W, Y, X, ctx=None):
+    """The plain linear model y_k ~ W + x per SNP (pg_lm_setup_dev + one pg_lm_x_dev / pg_lm_bed_dev call) on the GPU, from raw
+    genotypes.  W (n,c); Y (n,) or (n,t); X (n,p): a PackedBed, or an int8, uint8, float32 or float64 array that is handed over as
+    it is stored (C order: sample-major, Fortran order: SNP-major; anything else is copied to C order, other dtypes are cast to
+    float32).  Returns dict(beta, se_beta, tau, F_wald, p_wald) of (t, p) arrays (float32 x 3, float64 x 2)."""
+    from .bed import PackedBed
+    L = _lib.load()
+    with _lib.scope(ctx) as ctx:
+        W = _f32(W)
+        Y = np.asarray(Y)
+        Yt = _f32(Y.reshape(Y.shape[0], -1).T)                 # phenotype-major rows
+        n, c = W.shape
+        t = Yt.shape[0]
+        packed = isinstance(X, PackedBed)
+        if not packed:
+            X = np.asarray(X)
+            if X.dtype not in _LM_DTYPES:
+                X = X.astype(np.float32)
+            if not (X.flags.c_contiguous or X.flags.f_contiguous):
+                X = np.ascontiguousarray(X)
+        assert Yt.shape[1] == n and X.shape[0] == n
+        p = X.shape[1]
+        dW, dY = ctx.to_device(W), ctx.to_device(Yt)
+        work = ctx.alloc(max(int(L.pg_lm_work_bytes(n, c, t)), 256))
+        _lib.check(L.pg_lm_setup_dev(ctx.handle, n, c, t, dW.ptr, dY.ptr, n, work.ptr), "pg_lm_setup_dev")
+        out = [ctx.alloc(max(t * p, 1) * 4) for _ in range(3)] + [ctx.alloc(max(t * p, 1) * 8) for _ in range(2)]
+        if packed:
+            rec = np.ascontiguousarray(X.data)
+            dX = ctx.to_device(rec)
+            _lib.check(L.pg_lm_bed_dev(ctx.handle, n, c, t, p, dX.ptr, rec.shape[1], int(X.count_A1), work.ptr, *[b.ptr for b in out], p),
+                       "pg_lm_bed_dev")
+        else:
+            snp_major = X.flags.f_contiguous and not X.flags.c_contiguous
+            dX = ctx.to_device(X.T if snp_major else X)
+            _lib.check(L.pg_lm_x_dev(ctx.handle, n, c, t, p, dX.ptr, _LM_DTYPES[X.dtype], n if snp_major else p, int(snp_major), work.ptr,
+                                     *[b.ptr for b in out], p), "pg_lm_x_dev")
+        ctx.sync()
+        return {col: b.download((t, p), np.float32 if k < 3 else np.float64) for k, (col, b) in enumerate(zip(LM_COLS, out))}
+
+
 def gxe(d, Wr, yr, Xr, XEr, ctx=None, want_p=True, return_stats=False):
     """The SNP-by-environment Wald test (pg_assoc_gxe_dev) on the GPU: per SNP j, the REML Wald test of XEr[:, j] in
     y ~ Wr + Xr[:, j] + XEr[:, j], i.e. calculate(d, yr, [Wr, Xr[:, j]], XEr[:, j]) with lambda searched per SNP.
