@@ -20,6 +20,7 @@ result rows come back through a pinned buffer.  With several GPUs the eigenvecto
 RCCL broadcast over xGMI (pg_comm_*; no PyTorch).
 There is no CPU fallback: without the HIP library or a GPU this raises.
 """
+import contextlib
 import ctypes as C
 import json
 import os
@@ -33,8 +34,10 @@ import numpy as np
 import pandas as pd
 
 from . import _lib, dist
+from ._feed import _KIN_DTYPES, _Feed, _Pinned, _Ring, _describe, _genotypes, _put_window     # noqa: F401  (_KIN_DTYPES: re-exported)
 from ._lib import pin, pinned_empty     # noqa: F401  (re-exported: how a caller hands over pinned inputs)
 from .bed import PackedBed
+from .ops import LM_COLS as _LM_COLS
 from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_restricted, newton, the *_overload scalars)
 from . import model as _model
 
@@ -46,7 +49,6 @@ _WORKERS = 2             # host threads (each with its own stream and buffers) p
 _BATCH_MIN = 8192        # ... and at least, while the block is cut into up to _BATCH_COUNT batches: the first batch's DMA and the
 _BATCH_COUNT = 12        # last batch's kernels are the part of the loop that does not overlap (measured at p = 100 000: 4 batches
                          # 0.149-0.172 s, 8: 0.116, 12: 0.112, 16: 0.112 — tools/ab_stream_batch.py)
-_STAGE_THREADS = 8       # host copy threads per worker for the pageable -> pinned leg
 # Device bytes of X per GPU that may be copied in while the eigensolver runs.  OFF by default (0): with the caller's X in
 # hipHostMalloc'ed memory (pinned_empty) it takes the copy time out of the loop (p = 400 000 float32: 0.96 -> 0.90 s end to end), but
 # inside a long-lived process the first allocations after the eigensolver were seen to stall for ~0.15 s in one run out of four, and
@@ -54,6 +56,7 @@ _STAGE_THREADS = 8       # host copy threads per worker for the pageable -> pinn
 # with PYGEMMA_PREFETCH_MAX=1e11).  Opt-in: PYGEMMA_PREFETCH_MAX=<bytes>; only an X the caller pinned himself is prefetched.
 _PREFETCH_MAX = int(float(os.environ.get("PYGEMMA_PREFETCH_MAX", 0)))
 _PREFETCH_MARGIN = 8 << 30  # ... and what is left untouched beside the eigensolver's and the workers' buffers
+_U_PANEL_BYTES = 256 << 20  # eigenvectors given in pageable memory travel in row panels of this size through two pinned buffers
 
 
 class SampleIter:
@@ -115,52 +118,6 @@ def _block_fingerprint(X, s, e):
     n = X.shape[0]
     rows = np.unique(np.linspace(0, n - 1, min(n, 64)).astype(np.int64))
     return _crc(X[rows, s:e])
-
-
-class _Pinned:
-    """Pinned host buffers (hipHostMalloc through ctx), one per size in `sizes` (`.bufs`), freed together by close()."""
-
-    def __init__(self, ctx, *sizes):
-        self.ctx, self.bufs = ctx, []
-        try:
-            for nbytes in sizes:
-                p = C.c_void_p()
-                _lib.check(_lib.load().pg_host_alloc(ctx.handle, int(nbytes), C.byref(p)), "pg_host_alloc")
-                self.bufs.append(p.value)
-        except BaseException:
-            self.close()
-            raise
-
-    def close(self):
-        for q in self.bufs:
-            _lib.load().pg_host_free(self.ctx.handle, q)
-        self.bufs = []
-
-
-def _put_window(ctx, src, s, e, dst, dpitch=None, staging=None, threads=_STAGE_THREADS):
-    """SNPs [s, e) of a host source -> device address `dst`, in ONE DMA on ctx's stream.
-    `src` is an (n, p) array in C order (sample-major: n rows of the window's e - s values, landing `dpitch` bytes apart), or one
-    in F order or a PackedBed (SNP-major: e - s contiguous rows, one per SNP, landing back to back, or `dpitch` apart through a
-    2-D DMA when it is given).  Without `staging` src is pinned and the DMA reads it.  Otherwise `threads` copy threads first
-    gather the window into the pinned buffer `staging`: sample-major rows at `dpitch` (then the DMA is flat), SNP-major rows back
-    to back.  Waiting until `staging` or `dst` is free again is the caller's business."""
-    L = _lib.load()
-    if isinstance(src, PackedBed):
-        rec = np.ascontiguousarray(src.data[s:e])      # a view of the records, unless they are strided
-        snp_major, ptr, spitch, width, rows = True, rec.ctypes.data, rec.shape[1], rec.shape[1], e - s
-    elif src.flags.f_contiguous and not src.flags.c_contiguous:
-        width = src.shape[0] * src.itemsize
-        snp_major, ptr, spitch, rows = True, src.ctypes.data + s * width, width, e - s
-    else:
-        snp_major, ptr, spitch, width, rows = False, src.ctypes.data + s * src.itemsize, src.strides[0], (e - s) * src.itemsize, src.shape[0]
-    if staging is not None:
-        sp = width if snp_major else (dpitch or width)
-        _lib.check(L.pg_stage_rows(staging, sp, ptr, spitch, width, rows, threads), "pg_stage_rows")
-        ptr, spitch = staging, sp
-    if dpitch is None or (staging is not None and not snp_major):     # the rows lie as they will on the device
-        _lib.check(L.pg_memcpy_h2d_async(ctx.handle, dst, ptr, rows * (dpitch or width)), "pg_memcpy_h2d_async")
-    else:
-        _lib.check(L.pg_memcpy2d_h2d_async(ctx.handle, dst, dpitch, ptr, spitch, width, rows), "pg_memcpy2d_h2d_async")
 
 
 def _batch_geometry(n, a, b, gxe=False):
@@ -570,22 +527,11 @@ def kinship(G, standardize=True, device=0, *, snp_batch=None):
     called genotypes of its SNP, so K equals kinship(G.to_float(impute=True)) up to rounding; an all-missing SNP, where
     to_float gives NaN, is treated like a monomorphic one: it contributes zeros and still counts in p.
     With an array and `snp_batch` None, the whole float32 matrix is uploaded and handled at once (the original path)."""
-    if snp_batch is not None and (isinstance(snp_batch, bool) or not isinstance(snp_batch, (int, np.integer)) or snp_batch < 1):
-        raise ValueError(f"snp_batch must be a positive integer, not {snp_batch!r}")
-    if isinstance(G, PackedBed):
-        if G.n < 1 or G.p < 1:
-            raise ValueError(f"kinship needs at least one sample and one SNP: the PackedBed holds n={G.n}, p={G.p}")
-        return _kinship_stream(G, bool(standardize), device, snp_batch)
-    if snp_batch is not None:
-        G = np.asarray(G)
-        if G.ndim != 2:
-            raise ValueError(f"G must be a 2-D (n, p) array, not {G.ndim}-D")
-        if G.dtype not in _KIN_DTYPES:
-            raise ValueError(f"streamed kinship takes int8, uint8, float32 or float64 genotypes, not {G.dtype}")
+    _check_snp_batch(snp_batch)
+    if isinstance(G, PackedBed) or snp_batch is not None:
+        G = _genotypes(G, "streamed kinship", "G")
         if G.shape[0] < 1 or G.shape[1] < 1:
-            raise ValueError(f"kinship needs at least one sample and one SNP: G is {G.shape}")
-        if not (G.flags.c_contiguous or G.flags.f_contiguous):
-            G = np.ascontiguousarray(G)
+            raise ValueError(f"kinship needs at least one sample and one SNP: G holds n={G.shape[0]}, p={G.shape[1]}")
         return _kinship_stream(G, bool(standardize), device, snp_batch)
     L = _lib.load()
     G = np.ascontiguousarray(G, np.float32)
@@ -598,98 +544,62 @@ def kinship(G, standardize=True, device=0, *, snp_batch=None):
         return dK.download((n, n), np.float32)
 
 
-_KIN_DTYPES = {np.dtype(np.int8): 0, np.dtype(np.uint8): 1, np.dtype(np.float32): 2, np.dtype(np.float64): 3}   # PG_DTYPE_*
 # SNPs per batch by default: the fp64 read-modify-write of the accumulator (8 n^2 bytes per batch) against the batch's syrk
 # (2 n^2 pb fp16 flops on and below the diagonal) costs ~1 000 / pb of the batch at 5 TB/s and 1.2 PF: 6 % at 16 384
 _KIN_BATCH = 16384
 
 
+def _check_snp_batch(snp_batch):
+    if snp_batch is not None and (isinstance(snp_batch, bool) or not isinstance(snp_batch, (int, np.integer)) or snp_batch < 1):
+        raise ValueError(f"snp_batch must be a positive integer, not {snp_batch!r}")
+
+
+def _fit_batch(ctx, pb, auto, floor, need, who, what):
+    """SNPs per batch of a streamed scan: `pb`, with `auto` halved down to `floor` until the need(pb) device bytes fit into 0.9 of
+    what is free on ctx's GPU; a batch that does not fit is refused."""
+    free, _total = ctx.mem_info()
+    while auto and pb > floor and need(pb) > 0.9 * free:
+        pb = max(floor, pb // 2)
+    if need(pb) > free:
+        raise _lib.PgError(f"{who}, snp_batch={pb} needs {need(pb) / 2**30:.2f} GiB of device memory ({what}), "
+                           f"{free / 2**30:.2f} GiB free on GPU {ctx.device}")
+    return pb
+
+
 def _kinship_stream(G, standardize, device, snp_batch):
-    """The streamed kinship: SNP batches through pg_kinship_{bed,x}_acc_dev into one fp64 accumulator, then pg_kinship_finish_dev.
-    Uploads run on a second stream into two device slots, one batch ahead of the kernels, ordered by events."""
+    """The streamed kinship: SNP batches from the feed (_feed._Feed) through pg_kinship_{bed,x}_acc_dev into one fp64
+    accumulator, then pg_kinship_finish_dev."""
     L = _lib.load()
-    packed = isinstance(G, PackedBed)
-    n, p = (G.n, G.p) if packed else G.shape
-    if packed:
-        src_arr, row_bytes, snp_major, esz = G.data, G.data.shape[1], True, 1
-    else:
-        src_arr, esz = G, G.itemsize
-        snp_major = G.flags.f_contiguous and not G.flags.c_contiguous
-        row_bytes = n * esz
-    direct = _lib.is_pinned(src_arr) and (not packed or src_arr.flags.c_contiguous)
-    with _lib.Context(device) as ctx, _lib.Context(device) as up:
-        free, _total = ctx.mem_info()
-
-        def need(pb):
-            return int(L.pg_kinship_acc_bytes(n, pb)) + 4 * n * n + 2 * pb * row_bytes
-
-        if snp_batch is None:
-            pb = min(p, _KIN_BATCH)
-            while pb > 64 and need(pb) > 0.9 * free:
-                pb = max(64, pb // 2)
-        else:
-            pb = min(p, int(snp_batch))
-        if need(pb) > free:
-            raise _lib.PgError(f"kinship: n={n}, snp_batch={pb} needs {need(pb) / 2**30:.2f} GiB of device memory (fp64 accumulator "
-                               f"8 n^2, K 4 n^2, batch buffers), {free / 2**30:.2f} GiB free on GPU {device}")
+    src = _describe(G)
+    n, p = src.n, src.p
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
+        pb = _fit_batch(ctx, min(p, int(snp_batch or _KIN_BATCH)), snp_batch is None, 64,
+                        lambda pb: int(L.pg_kinship_acc_bytes(n, pb)) + 4 * n * n + 2 * pb * src.row_bytes,
+                        f"kinship: n={n}", "fp64 accumulator 8 n^2, K 4 n^2, batch buffers")
         dacc = ctx.alloc(L.pg_kinship_acc_bytes(n, pb))
         dK = ctx.alloc(4 * n * n)
-        slots = [ctx.alloc(pb * row_bytes) for _ in range(2)]
-        stg = _Pinned(up, *[pb * row_bytes] * (0 if direct else 2))
-        events = []
-        try:
-            for c_ in (up, up, ctx, ctx):
-                ev = C.c_void_p()
-                _lib.check(L.pg_event_create(c_.handle, C.byref(ev)), "pg_event_create")
-                events.append(ev)
-            ev_up, ev_done = events[:2], events[2:]
-            _lib.check(L.pg_memset(ctx.handle, dacc.ptr, 0, 8 * n * n), "pg_memset")
-            batches = [(s, min(s + pb, p)) for s in range(0, p, pb)]
-
-            def upload(b):
-                s, e = batches[b]
-                k = b % 2
-                if b >= 2:
-                    _lib.check(L.pg_stream_wait_event(up.handle, ev_done[k]), "pg_stream_wait_event")   # batch b-2 is done with the slot
-                    if not direct:
-                        _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")    # the DMA of batch b-2 has left the staging
-                # SNP-major: the records / columns [s, e) back to back; sample-major: the column window of every row at row stride e - s
-                _put_window(up, G, s, e, slots[k].ptr, None if snp_major else (e - s) * esz, None if direct else stg.bufs[k])
-                _lib.check(L.pg_event_record(up.handle, ev_up[k]), "pg_event_record")
-
-            upload(0)
-            for b, (s, e) in enumerate(batches):
-                k, w = b % 2, e - s
-                _lib.check(L.pg_stream_wait_event(ctx.handle, ev_up[k]), "pg_stream_wait_event")
-                if packed:
-                    _lib.check(L.pg_kinship_bed_acc_dev(ctx.handle, n, w, slots[k].ptr, row_bytes, int(G.count_A1), int(standardize), dacc.ptr),
-                               "pg_kinship_bed_acc_dev")
-                else:
-                    _lib.check(L.pg_kinship_x_acc_dev(ctx.handle, n, w, slots[k].ptr, _KIN_DTYPES[G.dtype], n if snp_major else w, int(snp_major),
-                                                      int(standardize), dacc.ptr), "pg_kinship_x_acc_dev")
-                _lib.check(L.pg_event_record(ctx.handle, ev_done[k]), "pg_event_record")
-                if b + 1 < len(batches):
-                    upload(b + 1)      # overlaps the kernels of batch b
-            _lib.check(L.pg_kinship_finish_dev(ctx.handle, n, p, dacc.ptr, dK.ptr), "pg_kinship_finish_dev")
-            ctx.sync()
-            return dK.download((n, n), np.float32)
-        finally:
-            up.sync()
-            ctx.sync()
-            for ev in events:
-                L.pg_event_destroy(up.handle, ev)
-            stg.close()
+        batches = feed.batches(pb)
+        _lib.check(L.pg_memset(ctx.handle, dacc.ptr, 0, 8 * n * n), "pg_memset")
+        for s, e, slot in batches:
+            if src.packed:
+                _lib.check(L.pg_kinship_bed_acc_dev(ctx.handle, n, e - s, slot, src.row_bytes, src.count_a1, int(standardize), dacc.ptr),
+                           "pg_kinship_bed_acc_dev")
+            else:
+                _lib.check(L.pg_kinship_x_acc_dev(ctx.handle, n, e - s, slot, src.dtype_code, n if src.snp_major else e - s,
+                                                  int(src.snp_major), int(standardize), dacc.ptr), "pg_kinship_x_acc_dev")
+        _lib.check(L.pg_kinship_finish_dev(ctx.handle, n, p, dacc.ptr, dK.ptr), "pg_kinship_finish_dev")
+        ctx.sync()
+        return dK.download((n, n), np.float32)
 
 
-_LM_COLS = ("beta", "se_beta", "tau", "F_wald", "p_wald")
 _LM_SLOT_BYTES = 256 << 20     # device bytes of one upload slot by default, and SNPs per batch at most: many batches, so that only the
 _LM_BATCH = 16384              # first upload (and, from pageable memory, the first staging copy) is exposed
 _CHI2_MEDIAN = 0.4549364       # chi2.ppf(0.5, 1)
 
 
-def _lm_columns(Y):
-    """(labels, float32 (t, n) phenotype-major matrix) of pygemma_lm's Y: (n,), (n, 1), (n, t) or a DataFrame, cast per column as
-    pygemma_multi casts it."""
+def _pheno_columns(Y):
+    """(labels, float32 columns) of a phenotype argument: (n,), (n, 1), (n, t) or a DataFrame (labelled by its columns, an array by
+    0..t-1), every column cast on its own as lmm.pygemma casts its Y (lmm.py:115-116)."""
     if isinstance(Y, pd.DataFrame):
         labels = list(Y.columns)
         cols = [np.asarray(Y.iloc[:, k]) for k in range(Y.shape[1])]
@@ -703,10 +613,15 @@ def _lm_columns(Y):
         cols = [Ya[:, k] for k in range(Ya.shape[1])]
     if not cols:
         raise ValueError("Y has no phenotype columns")
-    Yt = np.empty((len(cols), cols[0].shape[0]), np.float32)
-    for k, col in enumerate(cols):
-        Yt[k] = col.astype(np.float32)                       # lmm.py:115-116, per column
-    return labels, Yt
+    return labels, [col.astype(np.float32) for col in cols]
+
+
+def _frame(out, cols, snps, k=None):
+    """The result columns `cols` of `out` (with k: of phenotype k) as the DataFrame the reference returns (lmm.py:403-409)."""
+    df = pd.DataFrame({col: out[col] if k is None else out[col][k] for col in cols}, columns=list(cols))
+    if snps is not None:
+        df["SNPs"] = snps
+    return df
 
 
 def pygemma_lm(Y, X, W, snps=None, verbose=0, device=0, snp_batch=None, stats=None):
@@ -732,22 +647,14 @@ def pygemma_lm(Y, X, W, snps=None, verbose=0, device=0, snp_batch=None, stats=No
     batch boundaries.  `stats` receives batches, bytes_in, seconds and lambda_gc — per phenotype, median(chi2.isf(p_wald, 1)) /
     chi2.ppf(0.5, 1) over the non-NaN rows, as run_lin_reg.py computes it.  Refused with ValueError before any device work: shape
     mismatches, X not 2-D or of another dtype, W with other than 1..30 columns, c + t > 64, n - c - 1 <= 0, a bad snp_batch."""
-    if snp_batch is not None and (isinstance(snp_batch, bool) or not isinstance(snp_batch, (int, np.integer)) or snp_batch < 1):
-        raise ValueError(f"snp_batch must be a positive integer, not {snp_batch!r}")
-    packed = isinstance(X, PackedBed)
-    if not packed:
-        X = np.asarray(X)
-        if X.ndim != 2:
-            raise ValueError(f"X must be a 2-D (n, p) array, not {X.ndim}-D")
-        if X.dtype not in _KIN_DTYPES:
-            raise ValueError(f"pygemma_lm takes int8, uint8, float32 or float64 genotypes (or a PackedBed), not {X.dtype}")
-        if not (X.flags.c_contiguous or X.flags.f_contiguous):
-            X = np.ascontiguousarray(X)
+    _check_snp_batch(snp_batch)
+    X = _genotypes(X, "pygemma_lm")
     n, p = X.shape
     W = np.asarray(W)
     if W.ndim != 2 or not 1 <= W.shape[1] <= 30:
         raise ValueError(f"the linear model takes W with 1 to 30 columns, got W {W.shape}")
-    labels, Yt = _lm_columns(Y)
+    labels, cols = _pheno_columns(Y)
+    Yt = np.stack(cols)                                      # (t, n): phenotype-major rows
     t, c = len(labels), W.shape[1]
     if W.shape[0] != n or Yt.shape[1] != n:
         raise ValueError(f"shape mismatch: Y has {Yt.shape[1]} rows, X {n}, W {W.shape[0]}")
@@ -759,12 +666,7 @@ def pygemma_lm(Y, X, W, snps=None, verbose=0, device=0, snp_batch=None, stats=No
         raise ValueError(f"shape mismatch: {len(snps)} SNP names for {p} SNPs")
     W = np.ascontiguousarray(W.astype(np.float32))           # lmm.py:118-119
     out = _lm_stream(X, W, Yt, device, snp_batch, verbose, stats)
-    frames = {}
-    for k, lab in enumerate(labels):
-        df = pd.DataFrame({col: out[col][k] for col in _LM_COLS}, columns=list(_LM_COLS))
-        if snps is not None:
-            df["SNPs"] = snps
-        frames[lab] = df
+    frames = {lab: _frame(out, _LM_COLS, snps, k) for k, lab in enumerate(labels)}
     if stats is not None:
         from scipy import stats as _sps      # lazily, as model.py does
         lam = []
@@ -777,90 +679,35 @@ def pygemma_lm(Y, X, W, snps=None, verbose=0, device=0, snp_batch=None, stats=No
 
 
 def _lm_stream(X, W, Yt, device, snp_batch, verbose, stats):
-    """The streamed linear-model scan, modelled on _kinship_stream: pg_lm_setup_dev once, then SNP batches through pg_lm_{bed,x}_dev
-    into windows of the (t, p) result arrays on the device.  Uploads run on a second stream into two device slots, one batch ahead
-    of the kernels, ordered by events.  Returns the five (t, p) host arrays."""
+    """The streamed linear-model scan: pg_lm_setup_dev once, then SNP batches from the feed (_feed._Feed) through
+    pg_lm_{bed,x}_dev into windows of the (t, p) result arrays on the device.  Returns the five (t, p) host arrays."""
     L = _lib.load()
     t0 = time.time()
-    packed = isinstance(X, PackedBed)
-    (t, n), c = Yt.shape, W.shape[1]
-    p = X.p if packed else X.shape[1]
-    if packed:
-        src_arr, row_bytes, snp_major, esz = X.data, X.data.shape[1], True, 1
-    else:
-        src_arr, esz = X, X.itemsize
-        snp_major = X.flags.f_contiguous and not X.flags.c_contiguous
-        row_bytes = n * esz
-    direct = _lib.is_pinned(src_arr) and (not packed or src_arr.flags.c_contiguous)
+    src = _describe(X)
+    (t, n), c, p = Yt.shape, W.shape[1], src.p
     if _lib.device_count() < 1:
         raise _lib.PgError("no MI355X visible: pygemma_amd has no CPU path")
-    with _lib.Context(device) as ctx, _lib.Context(device) as up:
-        free, _total = ctx.mem_info()
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
         fixed = int(L.pg_lm_work_bytes(n, c, t)) + 28 * t * max(p, 1) + 4 * n * (c + t)
-
-        def need(pb):
-            return fixed + 2 * pb * row_bytes
-
-        if snp_batch is None:
-            pb = min(max(p, 1), _LM_BATCH, max(128, _LM_SLOT_BYTES // row_bytes // 128 * 128))
-            while pb > 128 and need(pb) > 0.9 * free:
-                pb = max(128, pb // 2)
-        else:
-            pb = min(max(p, 1), int(snp_batch))
-        if need(pb) > free:
-            raise _lib.PgError(f"pygemma_lm: n={n}, p={p}, t={t}, snp_batch={pb} needs {need(pb) / 2**30:.2f} GiB of device memory (panel, "
-                               f"{t} x {p} result rows, two batch slots), {free / 2**30:.2f} GiB free on GPU {device}")
+        pb = snp_batch or min(_LM_BATCH, max(128, _LM_SLOT_BYTES // src.row_bytes // 128 * 128))
+        pb = _fit_batch(ctx, min(max(p, 1), int(pb)), snp_batch is None, 128, lambda pb: fixed + 2 * pb * src.row_bytes,
+                        f"pygemma_lm: n={n}, p={p}, t={t}", f"panel, {t} x {p} result rows, two batch slots")
         dW, dY = ctx.to_device(W), ctx.to_device(Yt)
         work = ctx.alloc(L.pg_lm_work_bytes(n, c, t))
         _lib.check(L.pg_lm_setup_dev(ctx.handle, n, c, t, dW.ptr, dY.ptr, n, work.ptr), "pg_lm_setup_dev")
         res = [ctx.alloc(max(t * p, 1) * (4 if k < 3 else 8)) for k in range(5)]
-        slots = [ctx.alloc(pb * row_bytes) for _ in range(2)]
-        stg = _Pinned(up, *[pb * row_bytes] * (0 if direct else 2))
-        events = []
-        batches = [(s, min(s + pb, p)) for s in range(0, p, pb)]
-        try:
-            for c_ in (up, up, ctx, ctx):
-                ev = C.c_void_p()
-                _lib.check(L.pg_event_create(c_.handle, C.byref(ev)), "pg_event_create")
-                events.append(ev)
-            ev_up, ev_done = events[:2], events[2:]
-
-            def upload(b):
-                s, e = batches[b]
-                k = b % 2
-                if b >= 2:
-                    _lib.check(L.pg_stream_wait_event(up.handle, ev_done[k]), "pg_stream_wait_event")   # batch b-2 is done with the slot
-                    if not direct:
-                        _lib.check(L.pg_event_sync(up.handle, ev_up[k]), "pg_event_sync")    # the DMA of batch b-2 has left the staging
-                # SNP-major: the records / columns [s, e) back to back; sample-major: the column window of every row at row stride e - s
-                _put_window(up, X, s, e, slots[k].ptr, None if snp_major else (e - s) * esz, None if direct else stg.bufs[k])
-                _lib.check(L.pg_event_record(up.handle, ev_up[k]), "pg_event_record")
-
-            if batches:
-                upload(0)
-            for b, (s, e) in enumerate(batches):
-                k, w = b % 2, e - s
-                _lib.check(L.pg_stream_wait_event(ctx.handle, ev_up[k]), "pg_stream_wait_event")
-                win = [r.ptr + s * (4 if j < 3 else 8) for j, r in enumerate(res)]      # SNPs [s, e) of every phenotype's row: ldo = p
-                if packed:
-                    _lib.check(L.pg_lm_bed_dev(ctx.handle, n, c, t, w, slots[k].ptr, row_bytes, int(X.count_A1), work.ptr, *win, p), "pg_lm_bed_dev")
-                else:
-                    _lib.check(L.pg_lm_x_dev(ctx.handle, n, c, t, w, slots[k].ptr, _KIN_DTYPES[X.dtype], n if snp_major else w, int(snp_major),
-                                             work.ptr, *win, p), "pg_lm_x_dev")
-                _lib.check(L.pg_event_record(ctx.handle, ev_done[k]), "pg_event_record")
-                if b + 1 < len(batches):
-                    upload(b + 1)      # overlaps the kernels of batch b
-                _log(verbose - 1, f"linear model: SNPs [{s},{e}) queued")
-            ctx.sync()
-            out = {col: r.download((t, p), np.float32 if j < 3 else np.float64) for j, (col, r) in enumerate(zip(_LM_COLS, res))}
-        finally:
-            up.sync()
-            ctx.sync()
-            for ev in events:
-                L.pg_event_destroy(up.handle, ev)
-            stg.close()
+        for s, e, slot in feed.batches(pb):
+            win = [r.ptr + s * (4 if j < 3 else 8) for j, r in enumerate(res)]      # SNPs [s, e) of every phenotype's row: ldo = p
+            if src.packed:
+                _lib.check(L.pg_lm_bed_dev(ctx.handle, n, c, t, e - s, slot, src.row_bytes, src.count_a1, work.ptr, *win, p), "pg_lm_bed_dev")
+            else:
+                _lib.check(L.pg_lm_x_dev(ctx.handle, n, c, t, e - s, slot, src.dtype_code, n if src.snp_major else e - s,
+                                         int(src.snp_major), work.ptr, *win, p), "pg_lm_x_dev")
+            _log(verbose - 1, f"linear model: SNPs [{s},{e}) queued")
+        ctx.sync()
+        out = {col: r.download((t, p), np.float32 if j < 3 else np.float64) for j, (col, r) in enumerate(zip(_LM_COLS, res))}
     if stats is not None:
-        stats.update({"batches": len(batches), "bytes_in": p * row_bytes, "seconds": time.time() - t0})
+        stats.update({"batches": -(-p // pb), "bytes_in": p * src.row_bytes, "seconds": time.time() - t0})
     _log(verbose, f"Linear model: {p} SNPs x {t} phenotype(s) with {n} individuals in {time.time() - t0:.3f} s")
     return out
 
@@ -907,10 +754,7 @@ def pygemma(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, de=Fa
         raise NotImplementedError("de=True is broken in the reference (lmm/lmm.py:499) and is not provided")
     out = _scan(Y, X, W, K, Z=Z, verbose=verbose, disable_checks=disable_checks, grid=grid, eigen=eigen, nproc=nproc,
                 checkpoint=checkpoint, lrt=lrt, eigenpairs=eigenpairs, stats=stats)
-    results_df = pd.DataFrame(out, columns=list(out))                                                # lmm.py:403
-    if snps is not None:
-        results_df["SNPs"] = snps                                                                    # lmm.py:408-409
-    return results_df
+    return _frame(out, list(out), snps)
 
 
 def pygemma_multi(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, grid=False, eigen=True, nproc=1,
@@ -925,34 +769,14 @@ def pygemma_multi(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True,
     never dropped per phenotype: a NaN phenotype yields the rows a single run would give (disable_checks=False raises instead),
     the other phenotypes are unaffected — mean-impute missing values beforehand as the reference's callers do.  No lrt,
     checkpoint or de.  `stats` receives lmm.pygemma's counters plus `phenotypes`."""
-    if isinstance(Y, pd.DataFrame):
-        labels = list(Y.columns)
-        cols = [np.asarray(Y.iloc[:, k]) for k in range(Y.shape[1])]
-    else:
-        Ya = np.asarray(Y)
-        if Ya.ndim == 1:
-            Ya = Ya.reshape(-1, 1)
-        if Ya.ndim != 2:
-            raise ValueError(f"Y must be (n,) or (n, t), got shape {Ya.shape}")
-        labels = list(range(Ya.shape[1]))
-        cols = [Ya[:, k] for k in range(Ya.shape[1])]
-    if not cols:
-        raise ValueError("Y has no phenotype columns")
+    labels, cols = _pheno_columns(Y)
     n = X.shape[0]
     if cols[0].shape[0] != n:
         raise ValueError(f"shape mismatch: Y has {cols[0].shape[0]} rows, X {n}")
-    Y32 = np.empty((n, len(cols)), np.float32)
-    for k, col in enumerate(cols):
-        Y32[:, k] = col.astype(np.float32)                   # lmm.py:115-116, per column
+    Y32 = np.stack(cols, axis=1)
     out = _scan(Y32, X, W, K, Z=Z, verbose=verbose, disable_checks=disable_checks, grid=grid, eigen=eigen, nproc=nproc,
                 eigenpairs=eigenpairs, stats=stats, npheno=len(cols))
-    res = {}
-    for k, lab in enumerate(labels):
-        df = pd.DataFrame({col: out[col][k] for col in _COLS}, columns=list(_COLS))
-        if snps is not None:
-            df["SNPs"] = snps
-        res[lab] = df
-    return res
+    return {lab: _frame(out, _COLS, snps, k) for k, lab in enumerate(labels)}
 
 
 def pygemma_score(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True, eigen=True, nproc=1, eigenpairs=None, stats=None):
@@ -1032,10 +856,7 @@ def pygemma_gxe(Y, X, W, K, E, Z=None, snps=None, verbose=0, disable_checks=True
         raise ValueError(f"the interaction scan needs n - c - 3 > 0 (n = {n}, c = {c - 1} columns of W)")
     out = _scan(Y, X, We, K, Z=Z, verbose=verbose, disable_checks=disable_checks, eigen=True, nproc=nproc, eigenpairs=eigenpairs,
                 checkpoint=checkpoint, stats=stats, gxe=e)
-    results_df = pd.DataFrame(out, columns=list(out))
-    if snps is not None:
-        results_df["SNPs"] = snps
-    return results_df
+    return _frame(out, list(out), snps)
 
 
 def _null_lambda(L, n, c, d, Wr, yr):
@@ -1109,23 +930,11 @@ def _eigenbasis(L, ectx, n, Y, W, K, eigenpairs, ty, verbose, t0):
             _put_window(ectx, Uh.T, 0, n, dU0.ptr)
             ectx.sync()
         else:                      # pageable: row panels through two pinned buffers, copy threads ahead of the DMA
-            rows = max(1, min(n, (256 << 20) // (n * 4)))
-            halves = _Pinned(ectx, rows * n * 4, rows * n * 4)
-            try:
-                evs = [C.c_void_p(), C.c_void_p()]
-                for e_ in evs:
-                    _lib.check(L.pg_event_create(ectx.handle, C.byref(e_)), "pg_event_create")
+            rows = max(1, min(n, _U_PANEL_BYTES // (n * 4)))
+            with contextlib.closing(_Ring(ectx, rows * n * 4)) as ring:
                 for j, r0 in enumerate(range(0, n, rows)):
-                    k = j % 2
-                    if j >= 2:         # the DMA of panel j - 2 has left this buffer
-                        _lib.check(L.pg_event_sync(ectx.handle, evs[k]), "pg_event_sync")
-                    _put_window(ectx, Uh.T, r0, min(n, r0 + rows), dU0.ptr + r0 * n * 4, staging=halves.bufs[k])
-                    _lib.check(L.pg_event_record(ectx.handle, evs[k]), "pg_event_record")
+                    ring.put(j, Uh.T, r0, min(n, r0 + rows), dU0.ptr + r0 * n * 4)
                 ectx.sync()
-                for e_ in evs:
-                    L.pg_event_destroy(ectx.handle, e_)
-            finally:
-                halves.close()
         _log(verbose, f"Eigenvectors uploaded ({n * n * 4 / 1e9:.2f} GB) - {time.time() - t0:.3f} s")
     else:
         if K.shape != (n, n):

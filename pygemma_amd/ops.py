@@ -4,6 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._feed import _KIN_DTYPES, _genotypes
 
 
 def _f32(a):
@@ -74,7 +75,6 @@ def score(d, Wr, yr, Xr, lam0=None, ctx=None):
         return res
 
 
-_LM_DTYPES = {np.dtype(np.int8): 0, np.dtype(np.uint8): 1, np.dtype(np.float32): 2, np.dtype(np.float64): 3}   # PG_DTYPE_*
 LM_COLS = ("beta", "se_beta", "tau", "F_wald", "p_wald")
 
 
@@ -91,13 +91,8 @@ def lm(W, Y, X, ctx=None):
         Yt = _f32(Y.reshape(Y.shape[0], -1).T)                 # phenotype-major rows
         n, c = W.shape
         t = Yt.shape[0]
+        X = _genotypes(X, "ops.lm", cast=True)
         packed = isinstance(X, PackedBed)
-        if not packed:
-            X = np.asarray(X)
-            if X.dtype not in _LM_DTYPES:
-                X = X.astype(np.float32)
-            if not (X.flags.c_contiguous or X.flags.f_contiguous):
-                X = np.ascontiguousarray(X)
         assert Yt.shape[1] == n and X.shape[0] == n
         p = X.shape[1]
         dW, dY = ctx.to_device(W), ctx.to_device(Yt)
@@ -112,7 +107,7 @@ def lm(W, Y, X, ctx=None):
         else:
             snp_major = X.flags.f_contiguous and not X.flags.c_contiguous
             dX = ctx.to_device(X.T if snp_major else X)
-            _lib.check(L.pg_lm_x_dev(ctx.handle, n, c, t, p, dX.ptr, _LM_DTYPES[X.dtype], n if snp_major else p, int(snp_major), work.ptr,
+            _lib.check(L.pg_lm_x_dev(ctx.handle, n, c, t, p, dX.ptr, _KIN_DTYPES[X.dtype], n if snp_major else p, int(snp_major), work.ptr,
                                      *[b.ptr for b in out], p), "pg_lm_x_dev")
         ctx.sync()
         return {col: b.download((t, p), np.float32 if k < 3 else np.float64) for k, (col, b) in enumerate(zip(LM_COLS, out))}

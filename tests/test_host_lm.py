@@ -163,3 +163,47 @@ def test_contract_formulas_are_the_reference_ols_algebra():
         assert abs(rep["se_beta"][0, g] - se) <= 1e-10 * se, g
         assert abs(rep["F_wald"][0, g] - F) <= 1e-10 * F, g
         assert abs(rep["tau"][0, g] - (n - c - 1) / (resid @ resid)) <= 1e-10 * rep["tau"][0, g], g
+
+
+def _y_forms(n=20, t=3, seed=1):
+    """The phenotype arguments lmm._pheno_columns takes, as (Y, labels, float64 (n, t') matrix of its columns): those of
+    test_host_multi_pheno.py."""
+    import pandas as pd
+    Y = np.random.default_rng(seed).standard_normal((n, t)) * 1e3 + 1 / 3        # not float32 numbers: the cast rounds
+    return {"(n,)": (Y[:, 0], [0], Y[:, :1]), "(n, 1)": (Y[:, :1], [0], Y[:, :1]), "(n, t)": (Y, [0, 1, 2], Y),
+            "(n, t) F": (np.asfortranarray(Y), [0, 1, 2], Y), "float32": (Y.astype(np.float32), [0, 1, 2], Y.astype(np.float32)),
+            "frame": (pd.DataFrame(Y, columns=["bmi", "ldl", "hdl"]), ["bmi", "ldl", "hdl"], Y)}
+
+
+@pytest.mark.parametrize("form", ["(n,)", "(n, 1)", "(n, t)", "(n, t) F", "float32", "frame"])
+def test_every_phenotype_form_reaches_the_scan_as_float32_rows(form, monkeypatch):
+    """pygemma_lm takes the phenotype forms pygemma_multi takes (one lmm._pheno_columns): the scan gets their (t, n) float32 image."""
+    from pygemma_amd import lmm
+    _, X, W = _inputs()
+    Y, labels, cols = _y_forms()[form]
+    t, seen = len(labels), {}
+
+    def stream(X_, W_, Yt, *a):
+        seen["Y"] = Yt
+        return {col: np.arange(t * 5, dtype=np.float64).reshape(t, 5) for col in lmm._LM_COLS}
+
+    monkeypatch.setattr(lmm, "_lm_stream", stream)
+    res = lmm.pygemma_lm(Y, X, W, snps=list("abcde"))
+    assert seen["Y"].dtype == np.float32 and seen["Y"].shape == cols.T.shape and seen["Y"].flags.c_contiguous
+    assert (seen["Y"] == cols.T.astype(np.float32)).all()
+    frames = {labels[0]: res} if t == 1 else res
+    assert list(frames) == labels
+    for k, lab in enumerate(labels):
+        assert list(frames[lab].columns) == list(lmm._LM_COLS) + ["SNPs"] and list(frames[lab]["SNPs"]) == list("abcde")
+        assert (frames[lab]["beta"].to_numpy() == np.arange(5 * k, 5 * k + 5)).all()
+
+
+@pytest.mark.parametrize("bad", ["no columns", "3-D", "empty frame"])
+def test_bad_phenotype_matrix_is_refused_before_the_device(bad, monkeypatch):
+    import pandas as pd
+    from pygemma_amd import lmm
+    Y, X, W = _inputs()
+    Y = {"no columns": Y[:, :0], "3-D": Y[:, :, None], "empty frame": pd.DataFrame(index=range(20))}[bad]
+    _no_device(monkeypatch)
+    with pytest.raises(ValueError):
+        lmm.pygemma_lm(Y, X, W)

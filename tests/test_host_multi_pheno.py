@@ -83,3 +83,46 @@ def test_no_gpu_means_loud_failure_not_fallback():
     Y, X, W, d = _inputs()
     with pytest.raises(_lib.PgError):
         lmm.pygemma_multi(Y, X, W, d, eigen=False)
+
+
+def _y_forms(n=20, t=3, seed=1):
+    """The phenotype arguments lmm._pheno_columns takes, as (Y, labels, float64 (n, t') matrix of its columns)."""
+    import pandas as pd
+    Y = np.random.default_rng(seed).standard_normal((n, t)) * 1e3 + 1 / 3        # not float32 numbers: the cast rounds
+    return {"(n,)": (Y[:, 0], [0], Y[:, :1]), "(n, 1)": (Y[:, :1], [0], Y[:, :1]), "(n, t)": (Y, [0, 1, 2], Y),
+            "(n, t) F": (np.asfortranarray(Y), [0, 1, 2], Y), "float32": (Y.astype(np.float32), [0, 1, 2], Y.astype(np.float32)),
+            "frame": (pd.DataFrame(Y, columns=["bmi", "ldl", "hdl"]), ["bmi", "ldl", "hdl"], Y)}
+
+
+@pytest.mark.parametrize("form", ["(n,)", "(n, 1)", "(n, t)", "(n, t) F", "float32", "frame"])
+def test_every_phenotype_form_reaches_the_pipeline_as_float32_columns(form, monkeypatch):
+    from pygemma_amd import lmm
+    _, X, W, d = _inputs()
+    Y, labels, cols = _y_forms()[form]
+    seen = {}
+
+    def scan(Y32, *a, npheno, **k):
+        seen["Y"] = Y32
+        return {col: np.arange(npheno * 5, dtype=np.float64).reshape(npheno, 5) for col in lmm._COLS}
+
+    monkeypatch.setattr(lmm, "_scan", scan)
+    res = lmm.pygemma_multi(Y, X, W, d, eigen=False, snps=list("abcde"))
+    assert seen["Y"].dtype == np.float32 and seen["Y"].shape == cols.shape and seen["Y"].flags.c_contiguous
+    assert (seen["Y"] == cols.astype(np.float32)).all()
+    assert isinstance(res, dict) and list(res) == labels
+    for k, lab in enumerate(labels):
+        assert list(res[lab].columns) == list(lmm._COLS) + ["SNPs"] and list(res[lab]["SNPs"]) == list("abcde")
+        assert (res[lab]["beta"].to_numpy() == np.arange(5 * k, 5 * k + 5)).all()
+
+
+def test_pheno_columns_casts_per_column_and_refuses_what_is_no_phenotype_matrix():
+    import pandas as pd
+    from pygemma_amd import lmm
+    for form, (Y, labels, cols) in _y_forms().items():
+        got_labels, got = lmm._pheno_columns(Y)
+        assert got_labels == labels and len(got) == cols.shape[1], form
+        for k, col in enumerate(got):
+            assert col.dtype == np.float32 and col.ndim == 1 and (col == cols[:, k].astype(np.float32)).all(), (form, k)
+    for bad in (np.zeros((20, 0)), np.zeros((20, 2, 1)), np.float64(1.0), pd.DataFrame(index=range(20))):
+        with pytest.raises(ValueError):
+            lmm._pheno_columns(bad)
