@@ -212,6 +212,38 @@ int pg_lm_x_dev(pg_ctx *ctx, int64_t n, int c, int t, int64_t pb, const void *X,
 int pg_lm_bed_dev(pg_ctx *ctx, int64_t n, int c, int t, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, const void *work,
                   float *beta, float *se, float *tau, double *F, double *pval, int64_t ldo);
 
+/* ---- Per-SNP quality control from RAW genotypes (csrc/snp_stats.hip): what GEMMA's n_miss / af columns and its -miss / -maf / -hwe
+ * filters are made of, read once from the block as it is stored.  Block conventions of pg_lm_x_dev / pg_lm_bed_dev: an (n x pb)
+ * sample-major (snp_major = 0, ldX >= pb) or (pb x n) SNP-major (ldX >= n) block of dtype PG_DTYPE_*, or pb packed .bed records
+ * (ldb >= ceil(n/4) bytes; code convention and count_a1 of pg_rotate_bed_dev).  An element is first rounded to float32.
+ *   counts  : pb x 4 int64 {n_miss, n0, n1, n2}.  n_miss: .bed code 01, or a non-finite float element (an 8-bit block has no missing
+ *             code); n0, n1, n2: observed elements that are exactly 0, 1 or 2 (-0.0 is 0).  The .bed pad bits after sample n - 1 are
+ *             never counted.
+ *   moments : pb x 4 fp64 {mean, var, min, max} over the n_obs = n - n_miss observed values, var the population variance (ddof = 0);
+ *             all NaN with n_obs = 0.  A hard-call SNP (n0 + n1 + n2 == n_obs) takes them from the integers: S1 = n1 + 2 n2,
+ *             S2 = n1 + 4 n2, mean = (double)S1 / (double)n_obs, var = (double)(n_obs S2 - S1^2) / (double)(n_obs^2) — one correctly
+ *             rounded division each, the same bits from every storage.  Any other SNP takes fp64 two-pass moments (sum, then
+ *             sum of (x - mean)^2) in a fixed order, without floating-point atomics.
+ *             A row depends only on its SNP: not on pb, the row pitch, the batch boundaries or the run.
+ *   work    : device scratch of pg_snp_stats_work_bytes(n, pb) bytes (the chunk partials of a sample-major block); 0 for a refused shape.
+ *   pg_hwe_exact_dev : the exact Hardy-Weinberg test of Wigginton, Cutler and Abecasis (2005), two-sided, fp64, on p rows of counts of
+ *             n samples.  N = n0 + n1 + n2, nr = 2 min(n0, n2) + n1, nc = 2N - nr; the probabilities P(h) of h = nr mod 2, ..., nr
+ *             (step 2) heterozygotes are built unnormalised from the mode nr nc / 2N (raised by one to nr's parity) outward:
+ *             P(h - 2) = P(h) h (h - 1) / (4 (a + 1)(b + 1)), P(h + 2) = P(h) 4 a b / ((h + 2)(h + 1)), a = (nr - h) / 2, b = N - h - a;
+ *             pval = sum{P(h) : P(h) <= P(n1) (1 + 2^-30)} / sum P(h), at most 1 (the factor makes mathematically tied terms count
+ *             whichever way they were reached).  N = 0 -> NaN; monomorphic -> 1.0; a row with n_miss + n0 + n1 + n2 != n (not
+ *             hard-call) or a negative count -> NaN.
+ * PG_EINVAL for NULL pointers, n < 1, n >= 2^30, pb < 0, pb > 2^25 (p >= 2^31 for pg_hwe_exact_dev), a sample-major block of 2^24 or
+ * more workgroups (ceil(n / 256) chunks x ceil(pb / 256) column groups, ceil(pb / 128) for float64) or strides too small; PG_ENOTSUP
+ * for an unknown dtype: a refused call enqueues nothing.  pg_snp_stats_bed_dev and a SNP-major pg_snp_stats_x_dev do not touch work
+ * (any non-NULL pointer will do); only a sample-major block needs its pg_snp_stats_work_bytes. */
+size_t pg_snp_stats_work_bytes(int64_t n, int64_t pb);
+int pg_snp_stats_bed_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, void *work, int64_t *counts,
+                         double *moments);
+int pg_snp_stats_x_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, void *work, int64_t *counts,
+                       double *moments);
+int pg_hwe_exact_dev(pg_ctx *ctx, int64_t n, int64_t p, const int64_t *counts, double *pval);
+
 /* ---- SNP-by-environment interaction (GEMMA's -gxe): for SNP g with rotated genotype x = U'x_g and rotated interaction
  * xe = U'(x_g o e), the REML Wald test of xe in  y ~ W' + x + xe,  W' = the c shared covariates (the caller's W and U'e).
  * Row g is by definition calculate(d, yr, [W', x], xe) of pg_assoc_dev's arithmetic with c + 1 covariates (decade scan,

@@ -51,6 +51,25 @@ class PackedBed:
         data = np.memmap(prefix + ".bed", dtype=np.uint8, mode="r", offset=3, shape=(p, bpr))
         return cls(data, n, count_A1=count_A1, snps=snps)
 
+    def take(self, index):
+        """A new PackedBed over the selected SNP records: `index` is a boolean mask of length p (what lmm.snp_filter returns) or integer
+        indices in any order (negative ones count from the end).  One fancy-index copy of ceil(n/4) bytes per selected SNP; n and
+        count_A1 stay, `snps` follows the selection.  A mask of another length or an index outside the records raises ValueError."""
+        idx = np.asarray(index)
+        if idx.dtype == np.bool_:
+            if idx.shape != (self.p,):
+                raise ValueError(f"a mask over {self.p} SNPs has shape ({self.p},), not {idx.shape}")
+            idx = np.flatnonzero(idx)
+        else:
+            if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+                raise ValueError("index must be a boolean mask of length p or a 1-D array of integer SNP indices")
+            idx = idx.astype(np.int64)
+            if idx.size and (idx.min() < -self.p or idx.max() >= self.p):
+                raise ValueError(f"SNP index out of range for {self.p} SNPs")
+            idx = np.where(idx < 0, idx + self.p, idx)
+        snps = None if self.snps is None else [self.snps[j] for j in idx]
+        return PackedBed(np.ascontiguousarray(self.data[idx]), self.n, count_A1=self.count_A1, snps=snps)
+
     def to_float(self, impute=True):
         """Host decode to the (n, p) float32 matrix the reference's callers build (NaN or column-mean for missing calls)."""
         shifts = np.arange(4, dtype=np.uint8) * 2

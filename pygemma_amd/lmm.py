@@ -41,7 +41,8 @@ from .ops import LM_COLS as _LM_COLS
 from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_restricted, newton, the *_overload scalars)
 from . import model as _model
 
-__all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "SampleIter", "pinned_empty", "pin", "kinship"] + _model.__all__
+__all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
+           "kinship"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -710,6 +711,97 @@ def _lm_stream(X, W, Yt, device, snp_batch, verbose, stats):
         stats.update({"batches": -(-p // pb), "bytes_in": p * src.row_bytes, "seconds": time.time() - t0})
     _log(verbose, f"Linear model: {p} SNPs x {t} phenotype(s) with {n} individuals in {time.time() - t0:.3f} s")
     return out
+
+
+_STAT_COLS = ("n_obs", "n_miss", "n0", "n1", "n2", "miss", "mean", "var", "min", "max", "af", "maf", "hwe_p")
+
+
+def snp_stats(X, snps=None, hwe=True, device=0, snp_batch=None, verbose=0, stats=None):
+    """Per-SNP quality control from the raw genotypes, read once where they lie: what GEMMA prints as n_miss and af and filters on with
+    -miss, -maf and -hwe (calculate_allele_frequency_matrix and the MAF mask of the reference's callers, without a host pass).
+
+    X (n, p): whatever pygemma_lm takes — a PackedBed, or an int8, uint8, float32 or float64 array in C or Fortran order, pinned or
+    pageable — streamed in SNP batches of `snp_batch` columns through the two-slot feed; the results stay on the device until one
+    download at the end and do not depend on the batch boundaries.  Values are the scans' (float64 rounded to float32 per element); a
+    .bed code 01 and a NaN or +-Inf are missing, an 8-bit array has no missing code.  Returns a DataFrame of p rows (csrc/snp_stats.hip):
+      n_obs, n_miss, n0, n1, n2 (int64)  observed and missing calls; observed values that are exactly 0, 1, 2
+      miss                               n_miss / n
+      mean, var, min, max                of the observed values, var with ddof = 0; NaN with n_obs = 0.  A hard-call SNP
+                                         (n0 + n1 + n2 == n_obs) takes mean and var from the integer counts, one exact division each
+      af                                 mean / 2 where 0 <= min and max <= 2, else NaN (centred or standardised input has no allele
+                                         frequency): the frequency of the allele the input counts, A2 for a PackedBed unless count_A1
+      maf                                min(af, 1 - af)
+      hwe_p                              the exact Hardy-Weinberg test (Wigginton et al. 2005, two-sided) on n0, n1, n2; NaN for a SNP
+                                         that is not hard-call or has no observed call; the column is absent with hwe=False
+      SNPs                               `snps`, when given
+    `stats` receives batches, bytes_in, seconds.  Refused with ValueError before any device work: X not 2-D or of another dtype, an
+    empty X, `snps` of another length, a bad snp_batch.  snp_filter(st) turns the frame into GEMMA's default mask."""
+    _check_snp_batch(snp_batch)
+    X = _genotypes(X, "snp_stats")
+    n, p = X.shape
+    if n < 1 or p < 1:
+        raise ValueError(f"snp_stats needs at least one sample and one SNP: X holds n={n}, p={p}")
+    if snps is not None and len(snps) != p:
+        raise ValueError(f"shape mismatch: {len(snps)} SNP names for {p} SNPs")
+    cnt, mom, pv = _snp_stats_stream(X, bool(hwe), device, snp_batch, verbose, stats)
+    out = {"n_obs": n - cnt[:, 0], "n_miss": cnt[:, 0], "n0": cnt[:, 1], "n1": cnt[:, 2], "n2": cnt[:, 3], "miss": cnt[:, 0] / float(n),
+           "mean": mom[:, 0], "var": mom[:, 1], "min": mom[:, 2], "max": mom[:, 3]}
+    out["af"] = np.where((out["min"] >= 0) & (out["max"] <= 2), out["mean"] / 2, np.nan)
+    out["maf"] = np.minimum(out["af"], 1 - out["af"])
+    out["hwe_p"] = pv
+    return _frame(out, _STAT_COLS if hwe else _STAT_COLS[:-1], snps)
+
+
+def _snp_stats_stream(X, hwe, device, snp_batch, verbose, stats):
+    """The streamed QC pass: SNP batches from the feed (_feed._Feed) through pg_snp_stats_{bed,x}_dev into windows of the (p, 4) count
+    and moment arrays on the device, then pg_hwe_exact_dev on all p rows.  Returns the host arrays (counts, moments, hwe_p or None)."""
+    L = _lib.load()
+    t0 = time.time()
+    src = _describe(X)
+    n, p = src.n, src.p
+    if _lib.device_count() < 1:
+        raise _lib.PgError("no MI355X visible: pygemma_amd has no CPU path")
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
+        pb = snp_batch or min(_LM_BATCH, max(128, _LM_SLOT_BYTES // src.row_bytes // 128 * 128))
+        # only a sample-major block has chunk partials: records and SNP-major columns leave the work area untouched
+        work_bytes = (lambda pb: 256) if src.snp_major else (lambda pb: int(L.pg_snp_stats_work_bytes(n, pb)))
+        pb = _fit_batch(ctx, min(p, int(pb)), snp_batch is None, 128, lambda pb: 72 * p + 2 * pb * src.row_bytes + work_bytes(pb),
+                        f"snp_stats: n={n}, p={p}", "72 p bytes of results, two batch slots, chunk partials of a sample-major source")
+        work = ctx.alloc(work_bytes(pb))
+        dc, dm = ctx.alloc(32 * p), ctx.alloc(32 * p)
+        for s, e, slot in feed.batches(pb):
+            if src.packed:
+                _lib.check(L.pg_snp_stats_bed_dev(ctx.handle, n, e - s, slot, src.row_bytes, src.count_a1, work.ptr, dc.ptr + 32 * s, dm.ptr + 32 * s),
+                           "pg_snp_stats_bed_dev")
+            else:
+                _lib.check(L.pg_snp_stats_x_dev(ctx.handle, n, e - s, slot, src.dtype_code, n if src.snp_major else e - s, int(src.snp_major),
+                                                work.ptr, dc.ptr + 32 * s, dm.ptr + 32 * s), "pg_snp_stats_x_dev")
+            _log(verbose - 1, f"snp_stats: SNPs [{s},{e}) queued")
+        if hwe:
+            dp = ctx.alloc(8 * p)
+            _lib.check(L.pg_hwe_exact_dev(ctx.handle, n, p, dc.ptr, dp.ptr), "pg_hwe_exact_dev")
+        ctx.sync()
+        out = dc.download((p, 4), np.int64), dm.download((p, 4), np.float64), dp.download((p,), np.float64) if hwe else None
+    if stats is not None:
+        stats.update({"batches": -(-p // pb), "bytes_in": p * src.row_bytes, "seconds": time.time() - t0})
+    _log(verbose, f"SNP statistics: {p} SNPs with {n} individuals in {time.time() - t0:.3f} s")
+    return out
+
+
+def snp_filter(st, maf=0.01, miss=0.05, hwe=0.0):
+    """The boolean keep-mask GEMMA's filters give (defaults: -maf 0.01, -miss 0.05, no -hwe) on a frame of snp_stats; pure NumPy.  A SNP
+    stays with miss <= `miss`, var > 0 (polymorphic, at least one observed call), maf >= `maf` (a NaN maf fails unless `maf` is 0) and,
+    when `hwe` > 0, hwe_p >= `hwe` or hwe_p NaN (no test: not hard-call).  Equality keeps the SNP.  Hand the mask to PackedBed.take or
+    index the columns of X with it."""
+    keep = (st["miss"].to_numpy() <= miss) & (st["var"].to_numpy() > 0)
+    if maf != 0:
+        keep &= st["maf"].to_numpy() >= maf
+    if hwe > 0:
+        if "hwe_p" not in st:
+            raise ValueError("snp_filter(hwe > 0) needs the hwe_p column: call snp_stats with hwe=True")
+        pv = st["hwe_p"].to_numpy()
+        keep &= (pv >= hwe) | np.isnan(pv)
+    return keep
 
 
 def _zkzt(L, Z, K):
