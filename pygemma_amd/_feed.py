@@ -1,6 +1,6 @@
 """Host -> device transport of genotype windows: pinned staging buffers (_Pinned), one window in one DMA (_put_window), what a
-streamed consumer needs to know of its source (_describe), and the two-slot feed every streamed entry point of lmm.py reads its
-SNP batches from (_Feed: lmm.kinship, lmm.pygemma_lm; its staging half, _Ring, also carries a pageable U)."""
+streamed consumer needs to know of its source (_describe) and how it calls its kernels on a batch of it (_call_dev), and the two-slot
+feed every streamed entry point of lmm.py reads its SNP batches from (_Feed; its staging half, _Ring, also carries a pageable U)."""
 import ctypes as C
 from collections import namedtuple
 
@@ -91,6 +91,17 @@ def _describe(X):
     n, p = X.shape
     snp_major = bool(X.flags.f_contiguous and not X.flags.c_contiguous)
     return _Source(X, False, snp_major, X.itemsize, n * X.itemsize, n, p, _KIN_DTYPES[X.dtype], None, _lib.is_pinned(X))
+
+
+def _call_dev(L, stem, src, head, slot, pb, tail):
+    """A streamed consumer's kernels on the `pb` SNPs of `src` at the device address `slot`: the entry point stem.format("bed") with
+    (*head, slot, bytes per record, count_A1, *tail) for packed records, stem.format("x") with (*head, slot, PG_DTYPE_*, ld, snp_major,
+    *tail) for an array, ld = n for SNP-major columns and pb for the column window of a sample-major block."""
+    if src.packed:
+        name, source = stem.format("bed"), (slot, src.row_bytes, src.count_a1)
+    else:
+        name, source = stem.format("x"), (slot, src.dtype_code, src.n if src.snp_major else pb, int(src.snp_major))
+    _lib.check(getattr(L, name)(*head, *source, *tail), name)
 
 
 def _event(ctx):

@@ -12,12 +12,11 @@ tau as float32; lambda, F_wald, p_wald as float64; SNPs as object when `snps` is
 `nproc` = number of GPUs to spread contiguous SNP blocks over, exactly like SampleIter's ceil(p/nproc)
 column blocks (lmm.py:427-434); results come back in block order = SNP order.
 
-Streaming (BASELINE configs 4-5): X never has to fit on a GPU.  Every GPU takes its block in batches; a batch is DMA'd
-from PINNED host memory (directly out of X: the caller's own pinned array — `pinned_empty`/`pin` — or X page-locked in place
-for the duration of the call; a pinned staging buffer filled by copy threads only where that fails) on one stream while the
-previous batch computes on another, and its 32-byte
-result rows come back through a pinned buffer.  With several GPUs the eigenvectors travel once, GPU 0 -> all, as one
-RCCL broadcast over xGMI (pg_comm_*; no PyTorch).
+Streaming (BASELINE configs 4-5): X never has to fit on a GPU.  Every GPU takes its block in batches; a batch is DMA'd from
+PINNED host memory (directly out of X: the caller's own pinned array — `pinned_empty`/`pin` — or X page-locked in place for
+the duration of the call; a pinned staging buffer filled by copy threads only where that fails) on one stream while the
+previous batch computes on another, and its 32-byte result rows come back through a pinned buffer.  With several GPUs the
+eigenvectors travel once, GPU 0 -> all, as one RCCL broadcast over xGMI (pg_comm_*; no PyTorch).
 There is no CPU fallback: without the HIP library or a GPU this raises.
 """
 import contextlib
@@ -34,10 +33,10 @@ import numpy as np
 import pandas as pd
 
 from . import _lib, dist
-from ._feed import _KIN_DTYPES, _Feed, _Pinned, _Ring, _describe, _genotypes, _put_window     # noqa: F401  (_KIN_DTYPES: re-exported)
+from ._feed import _KIN_DTYPES, _Feed, _Pinned, _Ring, _call_dev, _describe, _genotypes, _put_window     # noqa: F401  (_KIN_DTYPES: re-exported)
 from ._lib import pin, pinned_empty     # noqa: F401  (re-exported: how a caller hands over pinned inputs)
 from .bed import PackedBed
-from .ops import LM_COLS as _LM_COLS
+from .ops import LM_COLS as _LM_COLS, _ldx
 from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_restricted, newton, the *_overload scalars)
 from . import model as _model
 
@@ -87,7 +86,7 @@ def _log(verbose, msg):
 def _rotate_small(ctx, L, n, dU, A):
     """U.T @ A for a narrow host matrix A (n,q) (Y and W): same MFMA kernel, SNP-major result transposed back."""
     q = A.shape[1]
-    ldx = (n + 63) // 64 * 64
+    ldx = _ldx(n)
     with _lib.scope(ctx):
         dA = ctx.to_device(np.ascontiguousarray(A, np.float32))
         dO = ctx.alloc(q * ldx * 4)
@@ -108,23 +107,21 @@ def _crc(a):
     return int(zlib.crc32(np.ascontiguousarray(a).view(np.uint8).reshape(-1)))
 
 
-def _block_fingerprint(X, s, e):
+def _block_fingerprint(src, s, e):
     """Cheap identity of the raw SNP block [s, e): CRC-32 of 64 evenly spaced sample rows (of byte columns for packed
     records).  Stored in every checkpoint part and compared before a part is restored, so that parts of a run on another
     genotype matrix of the same shape are refused instead of being mixed into the result."""
-    if isinstance(X, PackedBed):
-        rec = X.data[s:e]
-        step = max(1, rec.shape[1] // 64)
-        return _crc(rec[:, ::step])
-    n = X.shape[0]
-    rows = np.unique(np.linspace(0, n - 1, min(n, 64)).astype(np.int64))
-    return _crc(X[rows, s:e])
+    if src.packed:
+        rec = src.src.data[s:e]
+        return _crc(rec[:, ::max(1, src.row_bytes // 64)])
+    rows = np.unique(np.linspace(0, src.n - 1, min(src.n, 64)).astype(np.int64))
+    return _crc(src.src[rows, s:e])
 
 
 def _batch_geometry(n, a, b, gxe=False):
     """(SNPs per batch, row pitch in elements of a raw sample-major batch) for the block [a, b) of one GPU (`gxe`: the interaction
     scan, whose batches also hold the rotated x o e block)."""
-    ldx = (n + 63) // 64 * 64
+    ldx = _ldx(n)
     per_snp = (16 if gxe else 12) * ldx                               # raw block + rotated block + two fp16 planes [+ rotated x o e]
     pb_max = max(256, int(_BATCH_BYTES // per_snp) // 256 * 256)
     pb_max = min(pb_max, _BATCH_SNPS, b - a)
@@ -133,11 +130,7 @@ def _batch_geometry(n, a, b, gxe=False):
     return pb_max, (pb_max + 15) // 16 * 16
 
 
-class _View:
-    """A range of a device buffer (what a worker needs of a batch: its address)."""
-
-    def __init__(self, ptr):
-        self.ptr = ptr
+_View = namedtuple("_View", "ptr")      # a range of a device buffer (what a worker needs of a batch: its address)
 
 
 class _Prefetch:
@@ -148,8 +141,8 @@ class _Prefetch:
     buffers.  The SNP loop then takes those batches instead of issuing the copies: the loop runs at the kernels' rate, and at
     288 GB of HBM a 40 GB float32 X is resident before U is."""
 
-    def __init__(self, L, X, blocks, n, esz, verbose, gxe=False):
-        self.L, self.X, self.n, self.esz, self.verbose = L, X, n, esz, verbose
+    def __init__(self, L, src, blocks, verbose, gxe=False):
+        self.L, self.X, self.n, self.esz, self.verbose = L, src.src, src.n, src.esz, verbose
         self.lock = threading.Lock()
         self.ready = [dict() for _ in blocks]
         self.ctxs, self.plans = [], []
@@ -157,7 +150,7 @@ class _Prefetch:
         self.stop = False                        # set when the eigensolver is done: the batch in flight is the last one
         self.threads = []
         try:
-            self._plan(blocks, n, esz, gxe)
+            self._plan(blocks, gxe)
         except BaseException:                    # a context or buffer of GPU g failed: release those of the GPUs before it
             for ctx in self.ctxs:
                 ctx.close()
@@ -167,7 +160,8 @@ class _Prefetch:
         for th in self.threads:
             th.start()
 
-    def _plan(self, blocks, n, esz, gxe):
+    def _plan(self, blocks, gxe):
+        n, esz = self.n, self.esz
         for g, (a, b) in enumerate(blocks):
             ctx = _lib.Context(g)
             self.ctxs.append(ctx)
@@ -233,7 +227,7 @@ def _scan_mode(L, n, c, grid, lrt, npheno, lam0, gxe=False):
     last of them e; its launch takes the rotated x o e block as a sixth argument).  Each writes the 32-byte rows
     [F | p | beta | se | tau | lambda] of dist.result_columns, for npheno phenotype-major rows of pb SNPs with npheno; lrt appends
     [l_alt | l_null | D_lrt | p_lrt] in float64."""
-    ldx = (n + 63) // 64 * 64
+    ldx = _ldx(n)
     t = npheno or 1
 
     def rows(r0, m):      # the fields of m result rows at r0 in the kernels' argument order: beta, se, tau, lambda, F, p
@@ -280,10 +274,10 @@ def _scan_mode(L, n, c, grid, lrt, npheno, lam0, gxe=False):
 
 
 # The per-call invariants every GPU's block of a scan reads: eigenvalues d, rotated covariates Wr (n, c), rotated phenotype yr ((n,),
-# or (npheno, n) phenotype-major rows), X as _scan leaves it, the _Mode, the checkpoint directory, the stats dict, the _Prefetch
-# (each or None), the result columns `out` (filled in place) and `errs`, where the block and worker threads leave their exceptions, and
-# for the interaction scan the float32 environment `e` (n,) (None otherwise)
-_Job = namedtuple("_Job", "n c d Wr yr X grid eigen mode ckpt stats pre verbose out errs e", defaults=(None,))
+# or (npheno, n) phenotype-major rows), the _Source of X as _scan leaves it, the _Mode, the checkpoint directory, the stats dict, the
+# _Prefetch (each or None), the result columns `out` (filled in place) and `errs`, where the block and worker threads leave their
+# exceptions, and for the interaction scan the float32 environment `e` (n,) (None otherwise)
+_Job = namedtuple("_Job", "n c d Wr yr src grid eigen mode ckpt stats pre verbose out errs e", defaults=(None,))
 
 
 def _restore(job, device, a, b, pb_max):
@@ -296,7 +290,7 @@ def _restore(job, device, a, b, pb_max):
             todo.append((s, e))
             continue
         with np.load(part) as z:
-            if "fingerprint" not in z.files or int(z["fingerprint"]) != _block_fingerprint(job.X, s, e):
+            if "fingerprint" not in z.files or int(z["fingerprint"]) != _block_fingerprint(job.src, s, e):
                 raise ValueError(f"checkpoint part {part} was computed from different genotypes "
                                  f"(fingerprint of SNPs [{s},{e}) differs): refusing to mix runs")
             for col in job.mode.cols:
@@ -307,194 +301,212 @@ def _restore(job, device, a, b, pb_max):
 
 def _save_part(job, s, e):
     tmp = _part_path(job.ckpt, s, e) + ".tmp.npz"
-    np.savez(tmp, fingerprint=np.int64(_block_fingerprint(job.X, s, e)), **{col: job.out[col][s:e] for col in job.mode.cols})
+    np.savez(tmp, fingerprint=np.int64(_block_fingerprint(job.src, s, e)), **{col: job.out[col][s:e] for col in job.mode.cols})
     os.replace(tmp, _part_path(job.ckpt, s, e))
 
 
-def _run_block(job, device, a, b, dU, comm):
-    """One GPU: SNP columns [a,b) of X through (rotate | transpose) -> the kernels of job.mode, in batches.  Two host threads per
-    GPU, each with its own stream, device buffers and pinned staging, take batches from a shared list, so that the host->device
-    DMA of one batch overlaps the kernels of the other.  `dU`: GPU 0's resident eigenvectors (device 0) or None; with a
-    communicator the other GPUs receive them by RCCL broadcast.  With job.ckpt every finished batch is written to disk (and
-    batches found there, with a matching fingerprint of the raw block, are not redone)."""
-    n, X, eigen, stats, verbose = job.n, job.X, job.eigen, job.stats, job.verbose
+def _run_threads(target, argsets):      # one thread per argument tuple: all started, then all joined
+    threads = [threading.Thread(target=target, args=args) for args in argsets]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+
+
+def _stat_max(stats, key, since, lock=contextlib.nullcontext()):
+    if stats is not None:
+        with lock:
+            stats[key] = max(stats.get(key, 0.0), time.time() - since)
+
+
+def _rotation(L, src, eigen, n, ldx, ldX):
+    """The rotation of a block's batches, picked once (it depends on X's kind, `eigen` and PYGEMMA_ROTATE, not on the batch):
+    rot(ctx, w, pb, dXc, dU, dprep, dXr, xf) sends the pb SNPs whose raw block lies at dXc (pitch ldX), rotated by dU with its genotype
+    prep, to dXr (pitch ldx).  `xf`: a list the interaction scan's two rotations of a batch (U, then diag(e) U) share, empty at first."""
+    if src.packed:       # decode + impute + rotate for .bed records
+        def rot(ctx, w, pb, dXc, dU, dprep, dXr, xf):
+            _lib.check(L.pg_rotate_bed_dev(ctx.handle, n, pb, dprep.ptr, w.X.ptr, src.row_bytes, src.count_a1, dXr, ldx, w.work.ptr), "pg_rotate_bed_dev")
+    elif src.src.dtype == np.float64:
+        def rot(ctx, w, pb, dXc, dU, dprep, dXr, xf):
+            if not xf:       # the genotype check depends on X only: a block that failed it for U fails it for Ue
+                is_geno = C.c_int(0)
+                _lib.check(L.pg_rotate_geno_f64_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, ldX, dXr, ldx, w.work.ptr, C.byref(is_geno)), "pg_rotate_geno_f64_dev")
+                if is_geno.value:
+                    return
+                # off the genotype path: the block's float32 image in w.Xf (allocated with the first such block), cast once for both rotations
+                w.Xf = w.Xf or ctx.alloc(n * ldX * 4)
+                _lib.check(L.pg_cast_f64_f32_dev(ctx.handle, n, pb, dXc.ptr, ldX, w.Xf.ptr, ldX), "pg_cast_f64_f32_dev")
+                xf.append(True)
+            _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, w.Xf.ptr, ldX, dXr, ldx), "pg_rotate_dev")
+    elif src.src.dtype in (np.int8, np.uint8):      # 8-bit block (always finite): genotype codes or split planes, chosen on the device
+        def rot(ctx, w, pb, dXc, dU, dprep, dXr, xf):
+            _lib.check(L.pg_rotate_auto_i8_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, int(src.src.dtype == np.uint8), ldX, dXr, ldx, w.work.ptr, None),
+                       "pg_rotate_auto_i8_dev")
+    elif eigen and os.environ.get("PYGEMMA_ROTATE", "") == "fp32":      # the reference-arithmetic kernel for every block (tests, A/B)
+        def rot(ctx, w, pb, dXc, dU, dprep, dXr, xf):
+            _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, dXc.ptr, ldX, dXr, ldx), "pg_rotate_dev")
+    elif eigen:          # float32 block: path (genotype fp16x2 / split planes / fp32 MFMA) chosen on the device, no host wait
+        def rot(ctx, w, pb, dXc, dU, dprep, dXr, xf):
+            _lib.check(L.pg_rotate_auto_dev(ctx.handle, n, pb, dU.ptr, n, dprep.ptr, dXc.ptr, ldX, dXr, ldx, w.work.ptr, None), "pg_rotate_auto_dev")
+    elif not src.snp_major:      # eigen=False: rotated by the caller, only turned SNP-major
+        def rot(ctx, w, pb, dXc, dU, dprep, dXr, xf):
+            _lib.check(L.pg_transpose_dev(ctx.handle, n, pb, dXc.ptr, ldX, dXr, ldx), "pg_transpose_dev")
+    else:                # ... and SNP-major: the copy-in landed it in the layout the scan reads
+        def rot(ctx, w, pb, dXc, dU, dprep, dXr, xf):
+            pass
+    return rot
+
+
+def _block_setup(job, device, a, b, dU, comm, ctx0):
+    """What a GPU's workers share: U (broadcast first), the scan's invariants and the rotation's preps on the device, geometry, rotation."""
+    L, n, src = _lib.load(), job.n, job.src
+    if job.eigen and comm is not None:
+        # U: resident on GPU 0 (the eigensolver's output); the other GPUs get it over xGMI.  The collective comes before
+        # anything else of this thread that can fail (its receive buffer was allocated by the caller), so that no GPU is
+        # left waiting in the broadcast for a peer that has already given up.
+        t0 = time.time()
+        _lib.check(L.pg_comm_broadcast_dev(comm.handle, dU.ptr, n * n * 4, 0), "pg_comm_broadcast_dev")
+        ctx0.sync()
+        _log(job.verbose, f"GPU {device}: U ({n * n * 4 / 1e9:.2f} GB) broadcast over RCCL in {time.time() - t0:.3f} s")
+    g = SimpleNamespace(L=L, device=device, n=n, src=src, ldx=_ldx(n), gxe=job.e is not None, dU=dU, dprep=None, dUe=None, dprepe=None)
+    g.dev = tuple(ctx0.to_device(v).ptr for v in (job.d, job.Wr, job.yr))
+    if job.eigen:
+        # genotype fast path of the rotation (<= 3 equally spaced values per column), fp32 MFMA otherwise
+        g.dprep = ctx0.alloc(L.pg_geno_prep_bytes(n))
+        _lib.check(L.pg_geno_prep_dev(ctx0.handle, n, dU.ptr, n, g.dprep.ptr), "pg_geno_prep_dev")
+    if g.gxe:
+        # U'(x o e) = (diag(e) U)' x: Ue and its genotype prep, made on this GPU (after the broadcast of U), and every batch
+        # rotated twice, with (U, prep) into Xr and with (Ue, prep_e) into XEr
+        dE = ctx0.to_device(job.e)
+        g.dUe, g.dprepe = ctx0.alloc(n * n * 4), ctx0.alloc(L.pg_geno_prep_bytes(n))
+        _lib.check(L.pg_gxe_scale_u_dev(ctx0.handle, n, dU.ptr, n, dE.ptr, g.dUe.ptr), "pg_gxe_scale_u_dev")
+        _lib.check(L.pg_geno_prep_dev(ctx0.handle, n, g.dUe.ptr, n, g.dprepe.ptr), "pg_geno_prep_dev")
+    ctx0.sync()
+    g.pb_max, g.ldX = _batch_geometry(n, a, b, g.gxe)
+    # X itself is page-locked: DMA straight out of it.  Packed records are always staged here (_copy_in), even when pinned: whether the
+    # DMA could read them directly, as the feed does, is a change of its own with its own measurement.
+    g.direct = src.direct and not src.packed
+    g.rotate = _rotation(L, src, job.eigen, n, g.ldx, g.ldX)
+    return g
+
+
+def _copy_in(job, g, ctx, w, s, e):
+    """The raw block of SNPs [s, e) travels to the device, or landed there while the eigensolver ran: returns (where it is, prefetched)."""
+    dXc = job.pre.take(g.device, s, e) if job.pre is not None else None
+    if dXc is not None:
+        return dXc, True     # (a prefetched buffer is freed with the prefetcher: hipFree would drain the device here)
+    src, n = g.src, g.n
+    if src.packed:       # SNP records [s, e) of the .bed image, staged by one thread
+        _put_window(ctx, src.src, s, e, w.X.ptr, staging=w.inp, threads=1)
+    elif src.snp_major:  # SNPs [s, e) are pb contiguous rows of n floats (float32 only: _inputs sees to it)
+        dst, dpitch = (w.T.ptr, 4 * n) if job.eigen else (w.Xr.ptr, 4 * g.ldx)     # eigen=False: already the layout the scan reads
+        _put_window(ctx, src.src, s, e, dst, dpitch, w.inp)
+        if job.eigen:    # (pb x n) -> (n x ldX): the transposition kernel with the roles of n and p exchanged
+            _lib.check(g.L.pg_transpose_dev(ctx.handle, e - s, n, w.T.ptr, n, w.X.ptr, g.ldX), "pg_transpose_dev")
+    else:                # the column window [s, e) of every sample row, at row pitch ldX
+        _put_window(ctx, src.src, s, e, w.X.ptr, g.ldX * src.esz, w.inp)
+    return w.X, False
+
+
+def _batch(job, g, ctx, w, s, e):
+    """SNPs [s, e) on this worker's stream up to their result rows in w.out; returns (t_dma, prefetched)."""
+    pb = e - s
+    dXc, prefetched = _copy_in(job, g, ctx, w, s, e)
+    t_dma = time.time()
+    xf = []
+    g.rotate(ctx, w, pb, dXc, g.dU, g.dprep, w.Xr.ptr, xf)
+    if g.gxe:            # x o e: the same path on the same raw block, with Ue in U's place
+        g.rotate(ctx, w, pb, dXc, g.dUe, g.dprepe, w.XEr.ptr, xf)
+    job.mode.launch(ctx, g.dev, pb, w.Xr.ptr, w.res.ptr, *((w.XEr.ptr,) if g.gxe else ()))      # the mode's kernels, and the result rows back
+    _lib.check(g.L.pg_memcpy_d2h_async(ctx.handle, w.out, w.res.ptr, pb * job.mode.nout), "pg_memcpy_d2h_async")
+    ctx.sync()
+    return t_dma, prefetched
+
+
+def _worker_buffers(job, g, ctx, w):
+    """A worker's device buffers (w.X, T, Xr, res, work, XEr) and pinned ones (w.stg: staging w.inp unless the DMA reads X itself, result rows w.out)."""
+    n, src, pb_max, ldx, nout = g.n, g.src, g.pb_max, g.ldx, job.mode.nout
+    raw_bytes = pb_max * src.row_bytes if src.packed else n * g.ldX * src.esz
+    # one device allocation per worker, cut into its buffers: every hipMalloc / hipFree of a few hundred MB costs
+    # 1 - 2 ms of host time that nothing overlaps (r4: worker set-up 3.8 ms, teardown 9.2 ms with five allocations)
+    sizes = [raw_bytes, pb_max * n * 4 if (src.snp_major and not src.packed and job.eigen) else 0, pb_max * ldx * 4, pb_max * nout,
+             g.L.pg_geno_work_bytes(n, pb_max) if job.eigen else 0, pb_max * ldx * 4 if g.gxe else 0]
+    offs = np.concatenate([[0], np.cumsum([(int(z) + 255) // 256 * 256 for z in sizes])])
+    arena = ctx.alloc(int(offs[-1]))
+    for k, o, z in zip(("X", "T", "Xr", "res", "work", "XEr"), offs[:-1], sizes):
+        setattr(w, k, _View(arena.ptr + int(o)) if z else None)
+    w.stg = _Pinned(ctx, pb_max * nout) if g.direct else _Pinned(ctx, raw_bytes, pb_max * nout)
+    w.inp, w.out = (None, *w.stg.bufs) if g.direct else w.stg.bufs
+    w.hres = (C.c_char * (pb_max * nout)).from_address(w.out)
+
+
+def _worker(job, g):
+    """One of a GPU's host threads, with its own stream, device buffers and pinned staging, so that the host->device DMA of its batch
+    overlaps the kernels of the other's: batches off g.todo until it is empty or a thread has failed."""
     try:
-        L = _lib.load()
-        ctx0 = comm.ctx if comm is not None else _lib.Context(device)
-        t_blk = time.time()
+        ctx, stats = _lib.Context(g.device), job.stats
+        w = SimpleNamespace(stg=None, Xf=None)
+        t_w = time.time()
         try:
-            ldx = (n + 63) // 64 * 64
-            dprep = None
-            if eigen and comm is not None:
-                # U: resident on GPU 0 (the eigensolver's output); the other GPUs get it over xGMI.  The collective comes before
-                # anything else of this thread that can fail (its receive buffer was allocated by the caller), so that no GPU is
-                # left waiting in the broadcast for a peer that has already given up.
-                t0 = time.time()
-                _lib.check(L.pg_comm_broadcast_dev(comm.handle, dU.ptr, n * n * 4, 0), "pg_comm_broadcast_dev")
-                ctx0.sync()
-                _log(verbose, f"GPU {device}: U ({n * n * 4 / 1e9:.2f} GB) broadcast over RCCL in {time.time() - t0:.3f} s")
-            dev = tuple(ctx0.to_device(v).ptr for v in (job.d, job.Wr, job.yr))
-            if eigen:
-                # genotype fast path of the rotation (<= 3 equally spaced values per column), fp32 MFMA otherwise
-                dprep = ctx0.alloc(L.pg_geno_prep_bytes(n))
-                _lib.check(L.pg_geno_prep_dev(ctx0.handle, n, dU.ptr, n, dprep.ptr), "pg_geno_prep_dev")
-            gxe = job.e is not None
-            if gxe:
-                # U'(x o e) = (diag(e) U)' x: Ue and its genotype prep, made on this GPU (after the broadcast of U), and every batch
-                # rotated twice, with (U, prep) into Xr and with (Ue, prep_e) into XEr
-                dE = ctx0.to_device(job.e)
-                dUe, dprepe = ctx0.alloc(n * n * 4), ctx0.alloc(L.pg_geno_prep_bytes(n))
-                _lib.check(L.pg_gxe_scale_u_dev(ctx0.handle, n, dU.ptr, n, dE.ptr, dUe.ptr), "pg_gxe_scale_u_dev")
-                _lib.check(L.pg_geno_prep_dev(ctx0.handle, n, dUe.ptr, n, dprepe.ptr), "pg_geno_prep_dev")
-            ctx0.sync()
-            packed = isinstance(X, PackedBed)
-            x8 = (not packed) and X.dtype in (np.int8, np.uint8)
-            x64 = (not packed) and X.dtype == np.float64
-            force_fp32 = os.environ.get("PYGEMMA_ROTATE", "") == "fp32" and not (packed or x8 or x64)
-            esz = 1 if x8 else (8 if x64 else 4)
-            pb_max, ldX = _batch_geometry(n, a, b, gxe)
-            bpr = (n + 3) // 4
-            direct = (not packed) and _lib.is_pinned(X)        # X itself is page-locked: DMA straight out of it
-            snp_major = (not packed) and X.flags.f_contiguous and not X.flags.c_contiguous     # (float32 only: pygemma() sees to it)
-            nout = job.mode.nout
-            todo = _restore(job, device, a, b, pb_max)
-            lock = threading.Lock()
-            if stats is not None:
-                stats["setup_s"] = max(stats.get("setup_s", 0.0), time.time() - t_blk)
-
-            def batch(ctx, w, s, e):
-                """SNPs [s, e) on this worker's stream up to their result rows in w.out; returns (t_dma, prefetched)."""
-                pb = e - s
-                # ---- the raw block travels to the device (or landed there while the eigensolver ran); dXc: where it is
-                dXc = job.pre.take(device, s, e) if job.pre is not None else None
-                prefetched = dXc is not None
-                if not prefetched:
-                    dXc = w.X
-                    if packed:       # SNP records [s, e) of the .bed image, staged by one thread
-                        _put_window(ctx, X, s, e, w.X.ptr, staging=w.inp, threads=1)
-                    elif snp_major:  # SNPs [s, e) are pb contiguous rows of n floats
-                        dst, dpitch = (w.T.ptr, 4 * n) if eigen else (w.Xr.ptr, 4 * ldx)     # eigen=False: already the layout the scan reads
-                        _put_window(ctx, X, s, e, dst, dpitch, w.inp)
-                        if eigen:    # (pb x n) -> (n x ldX): the transposition kernel with the roles of n and p exchanged
-                            _lib.check(L.pg_transpose_dev(ctx.handle, pb, n, w.T.ptr, n, w.X.ptr, ldX), "pg_transpose_dev")
-                    else:            # the column window [s, e) of every sample row, at row pitch ldX
-                        _put_window(ctx, X, s, e, w.X.ptr, ldX * esz, w.inp)
-                t_dma = time.time()
-
-                # ---- rotation: decode + impute + rotate for .bed records; otherwise the path is chosen on the device
-                xf = []          # float64 block off the genotype path: its float32 image in w.Xf, cast once for both rotations
-
-                def rotate(dU, dprep, dXr):
-                    if packed:
-                        _lib.check(L.pg_rotate_bed_dev(ctx.handle, n, pb, dprep.ptr, w.X.ptr, bpr, int(X.count_A1), dXr, ldx,
-                                                       w.work.ptr), "pg_rotate_bed_dev")
-                    elif x64:
-                        if not xf:       # the genotype check depends on X only: a block that failed it for U fails it for Ue
-                            is_geno = C.c_int(0)
-                            _lib.check(L.pg_rotate_geno_f64_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, ldX, dXr, ldx, w.work.ptr,
-                                                                C.byref(is_geno)), "pg_rotate_geno_f64_dev")
-                            if is_geno.value:
-                                return
-                            w.Xf = w.Xf or ctx.alloc(n * ldX * 4)      # float32 image of a block that does not qualify for the genotype path
-                            _lib.check(L.pg_cast_f64_f32_dev(ctx.handle, n, pb, dXc.ptr, ldX, w.Xf.ptr, ldX), "pg_cast_f64_f32_dev")
-                            xf.append(True)
-                        _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, w.Xf.ptr, ldX, dXr, ldx), "pg_rotate_dev")
-                    elif x8:         # 8-bit block (always finite): genotype codes or split planes, chosen on the device
-                        _lib.check(L.pg_rotate_auto_i8_dev(ctx.handle, n, pb, dprep.ptr, dXc.ptr, int(X.dtype == np.uint8), ldX,
-                                                           dXr, ldx, w.work.ptr, None), "pg_rotate_auto_i8_dev")
-                    elif eigen and force_fp32:   # PYGEMMA_ROTATE=fp32: the reference-arithmetic kernel for every block (tests, A/B)
-                        _lib.check(L.pg_rotate_dev(ctx.handle, n, pb, dU.ptr, n, dXc.ptr, ldX, dXr, ldx), "pg_rotate_dev")
-                    elif eigen:      # float32 block: path (genotype fp16x2 / split planes / fp32 MFMA) chosen on the device, no host wait
-                        _lib.check(L.pg_rotate_auto_dev(ctx.handle, n, pb, dU.ptr, n, dprep.ptr, dXc.ptr, ldX, dXr, ldx,
-                                                        w.work.ptr, None), "pg_rotate_auto_dev")
-                    elif not snp_major:
-                        _lib.check(L.pg_transpose_dev(ctx.handle, n, pb, dXc.ptr, ldX, dXr, ldx), "pg_transpose_dev")
-
-                rotate(dU, dprep, w.Xr.ptr)
-                if gxe:          # x o e: the same path on the same raw block, with Ue in U's place
-                    rotate(dUe, dprepe, w.XEr.ptr)
-                # ---- the mode's kernels, and the result rows back
-                job.mode.launch(ctx, dev, pb, w.Xr.ptr, w.res.ptr, *((w.XEr.ptr,) if gxe else ()))
-                _lib.check(L.pg_memcpy_d2h_async(ctx.handle, w.out, w.res.ptr, pb * nout), "pg_memcpy_d2h_async")
-                ctx.sync()
-                return t_dma, prefetched     # (a prefetched buffer is freed with the prefetcher: hipFree would drain the device here)
-
-            def worker():
-                try:
-                    ctx = _lib.Context(device)
-                    stg = None
-                    t_w = time.time()
-                    try:
-                        raw_bytes = pb_max * bpr if packed else n * ldX * esz
-                        # one device allocation per worker, cut into its buffers: every hipMalloc / hipFree of a few hundred MB costs
-                        # 1 - 2 ms of host time that nothing overlaps (r4: worker set-up 3.8 ms, teardown 9.2 ms with five allocations)
-                        sizes = [raw_bytes, pb_max * n * 4 if (snp_major and eigen) else 0, pb_max * ldx * 4, pb_max * nout,
-                                 L.pg_geno_work_bytes(n, pb_max) if eigen else 0, pb_max * ldx * 4 if gxe else 0]
-                        offs = np.concatenate([[0], np.cumsum([(int(z) + 255) // 256 * 256 for z in sizes])])
-                        arena = ctx.alloc(int(offs[-1]))
-                        w = SimpleNamespace(**{k: _View(arena.ptr + int(o)) if z else None
-                                               for k, o, z in zip(("X", "T", "Xr", "res", "work", "XEr"), offs[:-1], sizes)}, Xf=None)
-                        stg = _Pinned(ctx, pb_max * nout) if direct else _Pinned(ctx, raw_bytes, pb_max * nout)
-                        w.inp, w.out = (None, *stg.bufs) if direct else stg.bufs
-                        hres = (C.c_char * (pb_max * nout)).from_address(w.out)
-                        if job.mode.warm is not None:
-                            job.mode.warm(ctx, pb_max)
-                        if stats is not None:
-                            with lock:
-                                stats["worker_alloc_s"] = max(stats.get("worker_alloc_s", 0.0), time.time() - t_w)
-                        while True:
-                            with lock:
-                                if not todo or job.errs:
-                                    return
-                                s, e = todo.pop(0)
-                            t_in = time.time()
-                            t_dma, prefetched = batch(ctx, w, s, e)
-                            t_ker = time.time()
-                            job.mode.decode(hres, job.out, s, e)
-                            if stats is not None:
-                                with lock:
-                                    if prefetched:
-                                        stats["prefetched_batches"] = stats.get("prefetched_batches", 0) + 1
-                                    stats["batches"] += 1
-                                    stats["bytes_in"] += (e - s) * bpr if packed else n * (e - s) * esz
-                                    stats["batch_s"] += time.time() - t_in
-                                    stats["dma_s"] = stats.get("dma_s", 0.0) + (t_dma - t_in)       # copy-in: staging + DMA issue
-                                    stats["kernel_s"] = stats.get("kernel_s", 0.0) + (t_ker - t_dma)
-                            if job.ckpt:
-                                _save_part(job, s, e)
-                            _log(verbose, f"GPU {device}: SNPs [{s},{e}) done")
-                    finally:
-                        t_td = time.time()
-                        if stg is not None:
-                            ctx.sync()
-                            stg.close()
-                        ctx.close()
-                        if stats is not None:
-                            with lock:
-                                stats["worker_teardown_s"] = max(stats.get("worker_teardown_s", 0.0), time.time() - t_td)
-                except Exception as ex:  # surfaced by the caller; never swallowed
-                    job.errs.append(ex)
-
-            workers = [threading.Thread(target=worker) for _ in range(min(_WORKERS, len(todo)))]
-            for th in workers:
-                th.start()
-            for th in workers:
-                th.join()
+            _worker_buffers(job, g, ctx, w)
+            if job.mode.warm is not None:
+                job.mode.warm(ctx, g.pb_max)
+            _stat_max(job.stats, "worker_alloc_s", t_w, g.lock)
+            while True:
+                with g.lock:
+                    if not g.todo or job.errs:
+                        return
+                    s, e = g.todo.pop(0)
+                t_in = time.time()
+                t_dma, prefetched = _batch(job, g, ctx, w, s, e)
+                t_ker = time.time()
+                job.mode.decode(w.hres, job.out, s, e)
+                if stats is not None:
+                    with g.lock:
+                        if prefetched:
+                            stats["prefetched_batches"] = stats.get("prefetched_batches", 0) + 1
+                        stats["batches"] += 1
+                        stats["bytes_in"] += (e - s) * g.src.row_bytes
+                        stats["batch_s"] += time.time() - t_in
+                        stats["dma_s"] = stats.get("dma_s", 0.0) + (t_dma - t_in)       # copy-in: staging + DMA issue
+                        stats["kernel_s"] = stats.get("kernel_s", 0.0) + (t_ker - t_dma)
+                if job.ckpt:
+                    _save_part(job, s, e)
+                _log(job.verbose, f"GPU {g.device}: SNPs [{s},{e}) done")
         finally:
             t_td = time.time()
-            if comm is None:
-                ctx0.close()
-            if stats is not None:
-                stats["block_teardown_s"] = max(stats.get("block_teardown_s", 0.0), time.time() - t_td)
+            if w.stg is not None:
+                ctx.sync()
+                w.stg.close()
+            ctx.close()
+            _stat_max(job.stats, "worker_teardown_s", t_td, g.lock)
     except Exception as ex:  # surfaced by the caller; never swallowed
         job.errs.append(ex)
 
 
-class _Comm:
-    """One communicator of a pg_comm_init_all group + the context it is bound to."""
+def _run_block(job, device, a, b, dU, comm):
+    """One GPU: SNP columns [a,b) of X through (rotate | transpose) -> the kernels of job.mode, in batches that _WORKERS host threads
+    take from a shared list.  `dU`: GPU 0's resident eigenvectors (device 0) or None; with a communicator the other GPUs receive them
+    by RCCL broadcast.  With job.ckpt every finished batch is written to disk (and batches found there, with a matching fingerprint
+    of the raw block, are not redone)."""
+    try:
+        ctx0 = comm.ctx if comm is not None else _lib.Context(device)
+        t_blk = time.time()
+        try:
+            g = _block_setup(job, device, a, b, dU, comm, ctx0)
+            g.todo, g.lock = _restore(job, device, a, b, g.pb_max), threading.Lock()
+            _stat_max(job.stats, "setup_s", t_blk)
+            _run_threads(_worker, [(job, g)] * min(_WORKERS, len(g.todo)))
+        finally:
+            t_td = time.time()
+            if comm is None:
+                ctx0.close()
+            _stat_max(job.stats, "block_teardown_s", t_td)
+    except Exception as ex:  # surfaced by the caller; never swallowed
+        job.errs.append(ex)
 
-    def __init__(self, handle, ctx):
-        self.handle, self.ctx = handle, ctx
+
+_Comm = namedtuple("_Comm", "handle ctx")     # one communicator of a pg_comm_init_all group + the context it is bound to
 
 
 def _make_comms(L, ndev):
@@ -555,9 +567,10 @@ def _check_snp_batch(snp_batch):
         raise ValueError(f"snp_batch must be a positive integer, not {snp_batch!r}")
 
 
-def _fit_batch(ctx, pb, auto, floor, need, who, what):
-    """SNPs per batch of a streamed scan: `pb`, with `auto` halved down to `floor` until the need(pb) device bytes fit into 0.9 of
-    what is free on ctx's GPU; a batch that does not fit is refused."""
+def _fit_batch(ctx, snp_batch, default, p, floor, need, who, what):
+    """SNPs per batch of a streamed scan over p SNPs: the caller's `snp_batch`, or `default` halved down to `floor` until the need(pb)
+    device bytes fit into 0.9 of what is free on ctx's GPU; a batch that does not fit is refused."""
+    pb, auto = min(p, int(snp_batch or default)), snp_batch is None
     free, _total = ctx.mem_info()
     while auto and pb > floor and need(pb) > 0.9 * free:
         pb = max(floor, pb // 2)
@@ -574,7 +587,7 @@ def _kinship_stream(G, standardize, device, snp_batch):
     src = _describe(G)
     n, p = src.n, src.p
     with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
-        pb = _fit_batch(ctx, min(p, int(snp_batch or _KIN_BATCH)), snp_batch is None, 64,
+        pb = _fit_batch(ctx, snp_batch, _KIN_BATCH, p, 64,
                         lambda pb: int(L.pg_kinship_acc_bytes(n, pb)) + 4 * n * n + 2 * pb * src.row_bytes,
                         f"kinship: n={n}", "fp64 accumulator 8 n^2, K 4 n^2, batch buffers")
         dacc = ctx.alloc(L.pg_kinship_acc_bytes(n, pb))
@@ -582,12 +595,7 @@ def _kinship_stream(G, standardize, device, snp_batch):
         batches = feed.batches(pb)
         _lib.check(L.pg_memset(ctx.handle, dacc.ptr, 0, 8 * n * n), "pg_memset")
         for s, e, slot in batches:
-            if src.packed:
-                _lib.check(L.pg_kinship_bed_acc_dev(ctx.handle, n, e - s, slot, src.row_bytes, src.count_a1, int(standardize), dacc.ptr),
-                           "pg_kinship_bed_acc_dev")
-            else:
-                _lib.check(L.pg_kinship_x_acc_dev(ctx.handle, n, e - s, slot, src.dtype_code, n if src.snp_major else e - s,
-                                                  int(src.snp_major), int(standardize), dacc.ptr), "pg_kinship_x_acc_dev")
+            _call_dev(L, "pg_kinship_{}_acc_dev", src, (ctx.handle, n, e - s), slot, e - s, (int(standardize), dacc.ptr))
         _lib.check(L.pg_kinship_finish_dev(ctx.handle, n, p, dacc.ptr, dK.ptr), "pg_kinship_finish_dev")
         ctx.sync()
         return dK.download((n, n), np.float32)
@@ -596,6 +604,22 @@ def _kinship_stream(G, standardize, device, snp_batch):
 _LM_SLOT_BYTES = 256 << 20     # device bytes of one upload slot by default, and SNPs per batch at most: many batches, so that only the
 _LM_BATCH = 16384              # first upload (and, from pageable memory, the first staging copy) is exposed
 _CHI2_MEDIAN = 0.4549364       # chi2.ppf(0.5, 1)
+
+
+def _gpus():     # how many are in sight; none is an error
+    ngpu = _lib.device_count()
+    if ngpu < 1:
+        raise _lib.PgError("no MI355X visible: pygemma_amd has no CPU path")
+    return ngpu
+
+
+def _lm_batch(src):     # SNPs per batch of the linear-model and QC streams by default: one upload slot's worth
+    return min(_LM_BATCH, max(128, _LM_SLOT_BYTES // src.row_bytes // 128 * 128))
+
+
+def _stream_stats(stats, src, pb, t0):
+    if stats is not None:
+        stats.update({"batches": -(-src.p // pb), "bytes_in": src.p * src.row_bytes, "seconds": time.time() - t0})
 
 
 def _pheno_columns(Y):
@@ -682,16 +706,13 @@ def pygemma_lm(Y, X, W, snps=None, verbose=0, device=0, snp_batch=None, stats=No
 def _lm_stream(X, W, Yt, device, snp_batch, verbose, stats):
     """The streamed linear-model scan: pg_lm_setup_dev once, then SNP batches from the feed (_feed._Feed) through
     pg_lm_{bed,x}_dev into windows of the (t, p) result arrays on the device.  Returns the five (t, p) host arrays."""
-    L = _lib.load()
-    t0 = time.time()
+    L, t0 = _lib.load(), time.time()
     src = _describe(X)
     (t, n), c, p = Yt.shape, W.shape[1], src.p
-    if _lib.device_count() < 1:
-        raise _lib.PgError("no MI355X visible: pygemma_amd has no CPU path")
+    _gpus()
     with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
         fixed = int(L.pg_lm_work_bytes(n, c, t)) + 28 * t * max(p, 1) + 4 * n * (c + t)
-        pb = snp_batch or min(_LM_BATCH, max(128, _LM_SLOT_BYTES // src.row_bytes // 128 * 128))
-        pb = _fit_batch(ctx, min(max(p, 1), int(pb)), snp_batch is None, 128, lambda pb: fixed + 2 * pb * src.row_bytes,
+        pb = _fit_batch(ctx, snp_batch, _lm_batch(src), max(p, 1), 128, lambda pb: fixed + 2 * pb * src.row_bytes,
                         f"pygemma_lm: n={n}, p={p}, t={t}", f"panel, {t} x {p} result rows, two batch slots")
         dW, dY = ctx.to_device(W), ctx.to_device(Yt)
         work = ctx.alloc(L.pg_lm_work_bytes(n, c, t))
@@ -699,16 +720,11 @@ def _lm_stream(X, W, Yt, device, snp_batch, verbose, stats):
         res = [ctx.alloc(max(t * p, 1) * (4 if k < 3 else 8)) for k in range(5)]
         for s, e, slot in feed.batches(pb):
             win = [r.ptr + s * (4 if j < 3 else 8) for j, r in enumerate(res)]      # SNPs [s, e) of every phenotype's row: ldo = p
-            if src.packed:
-                _lib.check(L.pg_lm_bed_dev(ctx.handle, n, c, t, e - s, slot, src.row_bytes, src.count_a1, work.ptr, *win, p), "pg_lm_bed_dev")
-            else:
-                _lib.check(L.pg_lm_x_dev(ctx.handle, n, c, t, e - s, slot, src.dtype_code, n if src.snp_major else e - s,
-                                         int(src.snp_major), work.ptr, *win, p), "pg_lm_x_dev")
+            _call_dev(L, "pg_lm_{}_dev", src, (ctx.handle, n, c, t, e - s), slot, e - s, (work.ptr, *win, p))
             _log(verbose - 1, f"linear model: SNPs [{s},{e}) queued")
         ctx.sync()
         out = {col: r.download((t, p), np.float32 if j < 3 else np.float64) for j, (col, r) in enumerate(zip(_LM_COLS, res))}
-    if stats is not None:
-        stats.update({"batches": -(-p // pb), "bytes_in": p * src.row_bytes, "seconds": time.time() - t0})
+    _stream_stats(stats, src, pb, t0)
     _log(verbose, f"Linear model: {p} SNPs x {t} phenotype(s) with {n} individuals in {time.time() - t0:.3f} s")
     return out
 
@@ -755,35 +771,26 @@ def snp_stats(X, snps=None, hwe=True, device=0, snp_batch=None, verbose=0, stats
 def _snp_stats_stream(X, hwe, device, snp_batch, verbose, stats):
     """The streamed QC pass: SNP batches from the feed (_feed._Feed) through pg_snp_stats_{bed,x}_dev into windows of the (p, 4) count
     and moment arrays on the device, then pg_hwe_exact_dev on all p rows.  Returns the host arrays (counts, moments, hwe_p or None)."""
-    L = _lib.load()
-    t0 = time.time()
+    L, t0 = _lib.load(), time.time()
     src = _describe(X)
     n, p = src.n, src.p
-    if _lib.device_count() < 1:
-        raise _lib.PgError("no MI355X visible: pygemma_amd has no CPU path")
+    _gpus()
     with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
-        pb = snp_batch or min(_LM_BATCH, max(128, _LM_SLOT_BYTES // src.row_bytes // 128 * 128))
         # only a sample-major block has chunk partials: records and SNP-major columns leave the work area untouched
         work_bytes = (lambda pb: 256) if src.snp_major else (lambda pb: int(L.pg_snp_stats_work_bytes(n, pb)))
-        pb = _fit_batch(ctx, min(p, int(pb)), snp_batch is None, 128, lambda pb: 72 * p + 2 * pb * src.row_bytes + work_bytes(pb),
+        pb = _fit_batch(ctx, snp_batch, _lm_batch(src), p, 128, lambda pb: 72 * p + 2 * pb * src.row_bytes + work_bytes(pb),
                         f"snp_stats: n={n}, p={p}", "72 p bytes of results, two batch slots, chunk partials of a sample-major source")
         work = ctx.alloc(work_bytes(pb))
         dc, dm = ctx.alloc(32 * p), ctx.alloc(32 * p)
         for s, e, slot in feed.batches(pb):
-            if src.packed:
-                _lib.check(L.pg_snp_stats_bed_dev(ctx.handle, n, e - s, slot, src.row_bytes, src.count_a1, work.ptr, dc.ptr + 32 * s, dm.ptr + 32 * s),
-                           "pg_snp_stats_bed_dev")
-            else:
-                _lib.check(L.pg_snp_stats_x_dev(ctx.handle, n, e - s, slot, src.dtype_code, n if src.snp_major else e - s, int(src.snp_major),
-                                                work.ptr, dc.ptr + 32 * s, dm.ptr + 32 * s), "pg_snp_stats_x_dev")
+            _call_dev(L, "pg_snp_stats_{}_dev", src, (ctx.handle, n, e - s), slot, e - s, (work.ptr, dc.ptr + 32 * s, dm.ptr + 32 * s))
             _log(verbose - 1, f"snp_stats: SNPs [{s},{e}) queued")
         if hwe:
             dp = ctx.alloc(8 * p)
             _lib.check(L.pg_hwe_exact_dev(ctx.handle, n, p, dc.ptr, dp.ptr), "pg_hwe_exact_dev")
         ctx.sync()
         out = dc.download((p, 4), np.int64), dm.download((p, 4), np.float64), dp.download((p,), np.float64) if hwe else None
-    if stats is not None:
-        stats.update({"batches": -(-p // pb), "bytes_in": p * src.row_bytes, "seconds": time.time() - t0})
+    _stream_stats(stats, src, pb, t0)
     _log(verbose, f"SNP statistics: {p} SNPs with {n} individuals in {time.time() - t0:.3f} s")
     return out
 
@@ -886,11 +893,7 @@ def pygemma_score(Y, X, W, K, Z=None, snps=None, verbose=0, disable_checks=True,
     lmm.pygemma's counters plus `lambda_null`."""
     out = _scan(Y, X, W, K, Z=Z, verbose=verbose, disable_checks=disable_checks, eigen=eigen, nproc=nproc, eigenpairs=eigenpairs,
                 stats=stats, score=True)
-    results_df = pd.DataFrame({"beta": out["beta"], "se_beta": out["se_beta"], "tau": out["tau"], "lambda": out["lambda"],
-                               "F_score": out["F_wald"], "p_score": out["p_wald"]})
-    if snps is not None:
-        results_df["SNPs"] = snps
-    return results_df
+    return _frame(out, list(out), snps).rename(columns={"F_wald": "F_score", "p_wald": "p_score"})
 
 
 def _e_in_span(W, e):
@@ -989,8 +992,7 @@ def _inputs(L, Y, X, W, K, Z, eigen, eigenpairs, score):
             K = K.astype(np.float32)                         # lmm.py:127-128
     # A Fortran-ordered float32 X is the SNP-major image (p rows of n samples): its batches are contiguous byte ranges that go to the
     # device as they are (and are turned sample-major there when they have to be rotated) — no transposing host copy of the matrix
-    snp_major = (not packed) and X.ndim == 2 and X.dtype == np.float32 and X.flags.f_contiguous and not X.flags.c_contiguous
-    if not packed and not X.flags.c_contiguous and not snp_major:
+    if not packed and not X.flags.c_contiguous and not (X.ndim == 2 and X.dtype == np.float32 and X.flags.f_contiguous):
         X = np.ascontiguousarray(X)
     n, c = X.shape[0], W.shape[1]
     if Y.shape[0] != n or W.shape[0] != n:
@@ -1072,43 +1074,39 @@ def _scan(Y, X, W, K, *, Z=None, verbose=0, disable_checks=True, grid=False, eig
     column of W).  Returns the result columns: arrays of p values, or npheno x p with npheno > 0."""
     L = _lib.load()
     Y, X, W, K = _inputs(L, Y, X, W, K, Z, eigen, eigenpairs, score)
-    packed = isinstance(X, PackedBed)
     nproc = min(int(nproc), X.shape[1])                      # lmm.py:113
-    n, p = X.shape
-    c = W.shape[1]
+    src = _describe(X)                                       # (src.direct: as X is now; settled once X has been page-locked below)
+    n, p, c = src.n, src.p, W.shape[1]
     ty = npheno or 1                                         # phenotype columns of Y that are used
-    ngpu = _lib.device_count()
-    if ngpu < 1:
-        raise _lib.PgError("no MI355X visible: pygemma_amd has no CPU path")
-    blocks = list(SampleIter(p, max(1, min(nproc, ngpu))))   # one contiguous block per GPU, none empty
+    blocks = list(SampleIter(p, max(1, min(nproc, _gpus()))))   # one contiguous block per GPU, none empty
     ndev = len(blocks)
 
     t0 = time.time()
     ectx = dU0 = None  # the eigensolver's context on GPU 0 and U resident there (reused by GPU 0's SNP loop)
     xpin = pre = pin_thread = comms = None
-    pin_box = {}       # page-locking of a pageable X beside the eigensolver
+    pin_box = {}       # page-locking of a pageable X, beside the eigensolver or before the blocks start
+
+    def page_lock():   # in place (hipHostRegister); a refusal is kept for the log
+        try:
+            pin_box["h"] = _lib.pin(X)
+        except _lib.PgError as ex:
+            pin_box["err"] = ex
     errs = []
     # ONE try/finally owns every resource made from here on (prefetch contexts and threads, the page-lock of X, the communicators,
     # the eigensolver's context): whatever raises in between — a bad K or U, NaNs, the manifest, a GPU's block — releases them all
     # in the order of the finally clause
     try:
-        if eigen and eigenpairs is None and not packed and not checkpoint and X.flags.c_contiguous and _PREFETCH_MAX > 0:
-            # the eigensolver leaves PCIe idle for ~0.6 s at n = 10 000 (52 s at 50 000): X starts moving now
+        if eigen and eigenpairs is None and not checkpoint and _PREFETCH_MAX > 0 and not src.snp_major and src.direct:
+            # the eigensolver leaves PCIe idle for ~0.6 s at n = 10 000 (52 s at 50 000): a pinned sample-major X starts moving now
             try:
-                if _lib.is_pinned(X):
-                    pre = _Prefetch(L, X, blocks, n, X.dtype.itemsize, verbose, gxe is not None)
+                pre = _Prefetch(L, src, blocks, verbose, gxe is not None)
             except _lib.PgError as ex:
                 _log(verbose, f"prefetch not started ({ex})")
-        if eigen and not packed and X.size and not _lib.is_pinned(X) and (X.flags.c_contiguous or X.flags.f_contiguous) and X.nbytes >= (256 << 20):
+        if eigen and not src.packed and not src.direct and X.nbytes >= (256 << 20):
             # Page-locking a pageable X in place costs ~0.06 s/GB the first time a range is registered (0.23 s for 4 GB: the kernel pins a million
             # pages; 2 ms on a repeat) — as long as the eigensolver runs anyway, it happens beside it on a thread of its own (r4: lmm.pygemma
             # from a pageable 4 GB X 0.77 -> ~0.5 s)
-            def _pin_bg():
-                try:
-                    pin_box["h"] = _lib.pin(X)
-                except _lib.PgError as ex:
-                    pin_box["err"] = ex
-            pin_thread = threading.Thread(target=_pin_bg, daemon=True)
+            pin_thread = threading.Thread(target=page_lock, daemon=True)
             pin_thread.start()
         if eigen:
             ectx = _lib.Context(0)
@@ -1122,16 +1120,13 @@ def _scan(Y, X, W, K, *, Z=None, verbose=0, disable_checks=True, grid=False, eig
         if not disable_checks:
             # lmm.py:253-256 (the reference tests the rotated arrays; a NaN anywhere in a raw column makes that
             # whole rotated column NaN, so testing the inputs raises in exactly the same cases)
-            if (not packed and X.dtype.kind == 'f' and np.isnan(X).any()) or np.isnan(Yr).any() or np.isnan(Wr).any():
+            if (not src.packed and X.dtype.kind == 'f' and np.isnan(X).any()) or np.isnan(Yr).any() or np.isnan(Wr).any():
                 raise ValueError("NaNs present in data")
 
         _log(verbose, f"Running {p} SNPs with {n} individuals on {ndev} GPU(s)...")
         shp = (npheno, p) if npheno else p
-        out = {"beta": np.empty(shp, np.float32), "se_beta": np.empty(shp, np.float32), "tau": np.empty(shp, np.float32),
-               "lambda": np.empty(shp, np.float64), "F_wald": np.empty(shp, np.float64), "p_wald": np.empty(shp, np.float64)}
-        if lrt:
-            for col in _LRT_COLS:
-                out[col] = np.empty(p, np.float64)
+        out = {col: np.empty(shp, np.float32 if k < 3 else np.float64) for k, col in enumerate(_COLS)}
+        out.update({col: np.empty(p, np.float64) for col in _LRT_COLS if lrt})
         if stats is not None:
             stats.update({"batches": 0, "bytes_in": 0, "batch_s": 0.0, "gpus": ndev})
             if npheno:
@@ -1160,33 +1155,25 @@ def _scan(Y, X, W, K, *, Z=None, verbose=0, disable_checks=True, grid=False, eig
                 stats["prefetched_bytes"] = int(pre.bytes)
         if pin_thread is not None:
             pin_thread.join()
-            xpin = pin_box.pop("h", None)
-            if "err" in pin_box:
-                _log(verbose, f"X could not be page-locked in place ({pin_box['err']}); staging through pinned buffers")
-        elif not packed and not _lib.is_pinned(X):
+        elif not src.packed and not src.direct:
             # page-lock the caller's X in place for the duration of the scan (hipHostRegister: 2 ms/GB for a range the kernel has pinned
             # before, ~60 ms/GB the first time: tools/probe_pageable.py) so that every batch is one 2-D DMA straight out of it; if the
             # range cannot be registered (e.g. a read-only file mapping) the workers fall back to copy threads + a pinned staging buffer
-            try:
-                xpin = _lib.pin(X)
-            except _lib.PgError as ex:
-                _log(verbose, f"X could not be page-locked in place ({ex}); staging through pinned buffers")
-        if stats is not None:
-            stats["pinned_input"] = bool((not packed) and _lib.is_pinned(X))
-            stats["registered_in_place"] = xpin is not None
+            page_lock()
+        xpin = pin_box.pop("h", None)
+        if "err" in pin_box:
+            _log(verbose, f"X could not be page-locked in place ({pin_box['err']}); staging through pinned buffers")
+        src = src._replace(direct=src.direct or xpin is not None)
+        if stats is not None:      # (pinned_input: what the DMA reads directly here, see _block_setup)
+            stats.update(pinned_input=src.direct and not src.packed, registered_in_place=xpin is not None)
         dUs = [dU0] + [None] * (ndev - 1)
         if ndev > 1 and eigen:
             comms = _make_comms(L, ndev)      # RCCL communicator over the GPUs of this process: U goes GPU 0 -> all over xGMI
             for g in range(1, ndev):          # receive buffers made here: an allocation failure surfaces before any thread waits in the collective
                 dUs[g] = comms[g].ctx.alloc(n * n * 4)
-        job = _Job(n, c, eigenVals, Wr, yr1, X, grid, eigen, _scan_mode(L, n, c, grid, lrt, npheno, lam0, gxe is not None), checkpoint,
+        job = _Job(n, c, eigenVals, Wr, yr1, src, grid, eigen, _scan_mode(L, n, c, grid, lrt, npheno, lam0, gxe is not None), checkpoint,
                    stats, pre, verbose, out, errs, gxe)
-        threads = [threading.Thread(target=_run_block, args=(job, g, a, b, dUs[g], comms[g] if comms else None))
-                   for g, (a, b) in enumerate(blocks)]
-        for th in threads:
-            th.start()
-        for th in threads:
-            th.join()
+        _run_threads(_run_block, [(job, g, a, b, dUs[g], comms[g] if comms else None) for g, (a, b) in enumerate(blocks)])
         if stats is not None:
             stats["blocks_s"] = time.time() - t2          # page-locking + every GPU's block; what follows is teardown (frees)
     finally:

@@ -4,11 +4,25 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._feed import _KIN_DTYPES, _genotypes
+from ._feed import _KIN_DTYPES, _call_dev, _describe, _genotypes     # noqa: F401  (_KIN_DTYPES: re-exported)
 
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _ldx(n):     # row pitch, in floats, of a rotated SNP-major block
+    return (n + 63) // 64 * 64
+
+
+def _six_alloc(ctx, p):     # device columns of a scan's p result rows: beta, se_beta, tau, lambda (float32), F, p (float64)
+    return [ctx.alloc(max(p, 1) * 4) for _ in range(4)] + [ctx.alloc(max(p, 1) * 8) for _ in range(2)]
+
+
+def _six_download(out, p, F, pv):     # ... as host arrays, the last two named `F` and `pv`, lambda widened as in the reference's frame
+    res = {col: b.download((p,), np.float32 if k < 4 else np.float64) for k, (col, b) in enumerate(zip(("beta", "se_beta", "tau", "lambda", F, pv), out))}
+    res["lambda"] = res["lambda"].astype(np.float64)
+    return res
 
 
 def assoc(d, Wr, yr, Xr, grid=False, ctx=None, want_p=True, return_stats=False):
@@ -62,15 +76,13 @@ def score(d, Wr, yr, Xr, lam0=None, ctx=None):
         lam0 = np.float32(lam0)
         dX = ctx.to_device(Xr)
         dXr = ctx.alloc(max(p, 1) * n * 4)
-        out = [ctx.alloc(max(p, 1) * 4) for _ in range(4)] + [ctx.alloc(max(p, 1) * 8) for _ in range(2)]
+        out = _six_alloc(ctx, p)
         if p:
             _lib.check(L.pg_transpose_dev(ctx.handle, n, p, dX.ptr, p, dXr.ptr, n), "pg_transpose_dev")
         _lib.check(L.pg_score_dev(ctx.handle, n, c, p, dd.ptr, dW.ptr, dy.ptr, float(lam0), dXr.ptr, n, *[b.ptr for b in out]),
                    "pg_score_dev")
         ctx.sync()
-        res = {col: b.download((p,), np.float32 if k < 4 else np.float64)
-               for k, (col, b) in enumerate(zip(("beta", "se_beta", "tau", "lambda", "F_score", "p_score"), out))}
-        res["lambda"] = res["lambda"].astype(np.float64)
+        res = _six_download(out, p, "F_score", "p_score")
         res["lambda_null"] = float(lam0)
         return res
 
@@ -79,11 +91,10 @@ LM_COLS = ("beta", "se_beta", "tau", "F_wald", "p_wald")
 
 
 def lm(W, Y, X, ctx=None):
-    """The plain linear model y_k ~ W + x per SNP (pg_lm_setup_dev + one pg_lm_x_dev / pg_lm_bed_dev call) on the GPU, from raw
+    """The plain linear model y_k ~ W + x per SNP (pg_lm_setup_dev + one pg_lm_{bed,x}_dev call) on the GPU, from raw
     genotypes.  W (n,c); Y (n,) or (n,t); X (n,p): a PackedBed, or an int8, uint8, float32 or float64 array that is handed over as
     it is stored (C order: sample-major, Fortran order: SNP-major; anything else is copied to C order, other dtypes are cast to
     float32).  Returns dict(beta, se_beta, tau, F_wald, p_wald) of (t, p) arrays (float32 x 3, float64 x 2)."""
-    from .bed import PackedBed
     L = _lib.load()
     with _lib.scope(ctx) as ctx:
         W = _f32(W)
@@ -91,24 +102,15 @@ def lm(W, Y, X, ctx=None):
         Yt = _f32(Y.reshape(Y.shape[0], -1).T)                 # phenotype-major rows
         n, c = W.shape
         t = Yt.shape[0]
-        X = _genotypes(X, "ops.lm", cast=True)
-        packed = isinstance(X, PackedBed)
-        assert Yt.shape[1] == n and X.shape[0] == n
-        p = X.shape[1]
+        src = _describe(_genotypes(X, "ops.lm", cast=True))
+        assert Yt.shape[1] == n and src.n == n
+        p = src.p
         dW, dY = ctx.to_device(W), ctx.to_device(Yt)
         work = ctx.alloc(max(int(L.pg_lm_work_bytes(n, c, t)), 256))
         _lib.check(L.pg_lm_setup_dev(ctx.handle, n, c, t, dW.ptr, dY.ptr, n, work.ptr), "pg_lm_setup_dev")
         out = [ctx.alloc(max(t * p, 1) * 4) for _ in range(3)] + [ctx.alloc(max(t * p, 1) * 8) for _ in range(2)]
-        if packed:
-            rec = np.ascontiguousarray(X.data)
-            dX = ctx.to_device(rec)
-            _lib.check(L.pg_lm_bed_dev(ctx.handle, n, c, t, p, dX.ptr, rec.shape[1], int(X.count_A1), work.ptr, *[b.ptr for b in out], p),
-                       "pg_lm_bed_dev")
-        else:
-            snp_major = X.flags.f_contiguous and not X.flags.c_contiguous
-            dX = ctx.to_device(X.T if snp_major else X)
-            _lib.check(L.pg_lm_x_dev(ctx.handle, n, c, t, p, dX.ptr, _KIN_DTYPES[X.dtype], n if snp_major else p, int(snp_major), work.ptr,
-                                     *[b.ptr for b in out], p), "pg_lm_x_dev")
+        dX = ctx.to_device(src.src.data if src.packed else src.src.T if src.snp_major else src.src)     # the whole source, as it is stored
+        _call_dev(L, "pg_lm_{}_dev", src, (ctx.handle, n, c, t, p), dX.ptr, p, (work.ptr, *[b.ptr for b in out], p))
         ctx.sync()
         return {col: b.download((t, p), np.float32 if k < 3 else np.float64) for k, (col, b) in enumerate(zip(LM_COLS, out))}
 
@@ -128,7 +130,7 @@ def gxe(d, Wr, yr, Xr, XEr, ctx=None, want_p=True, return_stats=False):
         dd, dW, dy = ctx.to_device(d), ctx.to_device(Wr), ctx.to_device(yr)
         dX, dXE = ctx.to_device(Xr), ctx.to_device(XEr)
         dXr, dXEr = ctx.alloc(max(p, 1) * n * 4), ctx.alloc(max(p, 1) * n * 4)
-        out = [ctx.alloc(max(p, 1) * 4) for _ in range(4)] + [ctx.alloc(max(p, 1) * 8) for _ in range(2)]
+        out = _six_alloc(ctx, p)
         dst = ctx.alloc(16)
         _lib.check(L.pg_memset(ctx.handle, dst.ptr, 0, 16), "pg_memset")
         if p:
@@ -137,9 +139,7 @@ def gxe(d, Wr, yr, Xr, XEr, ctx=None, want_p=True, return_stats=False):
         _lib.check(L.pg_assoc_gxe_dev(ctx.handle, n, c, p, dd.ptr, dW.ptr, dy.ptr, dXr.ptr, n, dXEr.ptr, n,
                                       *[b.ptr for b in out[:5]], out[5].ptr if want_p else None, dst.ptr), "pg_assoc_gxe_dev")
         ctx.sync()
-        res = {col: b.download((p,), np.float32 if k < 4 else np.float64)
-               for k, (col, b) in enumerate(zip(("beta", "se_beta", "tau", "lambda", "F_wald", "p_wald"), out))}
-        res["lambda"] = res["lambda"].astype(np.float64)
+        res = _six_download(out, p, "F_wald", "p_wald")
         if not want_p:
             res["p_wald"] = None
         if return_stats:
@@ -165,7 +165,7 @@ def rotate(U, X, ctx=None, ldx=None):
     with _lib.scope(ctx) as ctx:
         U, X = _f32(U), _f32(X)
         n, p = X.shape
-        ldx = ldx or (n + 63) // 64 * 64
+        ldx = ldx or _ldx(n)
         dU, dX = ctx.to_device(U), ctx.to_device(X)
         dXr = ctx.alloc(p * ldx * 4)
         _lib.check(L.pg_rotate_dev(ctx.handle, n, p, dU.ptr, n, dX.ptr, p, dXr.ptr, ldx), "pg_rotate_dev")
@@ -201,7 +201,7 @@ def rotate_geno(U, X, ctx=None, ldx=None):
     with _lib.scope(ctx) as ctx:
         U, X = _f32(U), _f32(X)
         n, p = X.shape
-        ldx = ldx or (n + 63) // 64 * 64
+        ldx = ldx or _ldx(n)
         dU, dX = ctx.to_device(U), ctx.to_device(X)
         dprep = ctx.alloc(L.pg_geno_prep_bytes(n))
         dwork = ctx.alloc(L.pg_geno_work_bytes(n, p))
@@ -221,7 +221,7 @@ def rotate_auto(U, X, ctx=None):
     with _lib.scope(ctx) as ctx:
         U, X = _f32(U), _f32(X)
         n, p = X.shape
-        ldx = (n + 63) // 64 * 64
+        ldx = _ldx(n)
         dU, dX = ctx.to_device(U), ctx.to_device(X)
         dprep, dwork = ctx.alloc(L.pg_geno_prep_bytes(n)), ctx.alloc(L.pg_geno_work_bytes(n, p))
         dXr, dpath = ctx.alloc(p * ldx * 4), ctx.alloc(4)

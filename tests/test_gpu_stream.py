@@ -243,6 +243,48 @@ def test_fortran_ordered_snp_major_X_streams_without_a_host_transpose(eigen, how
         assert (a.view(np.uint8) == b.view(np.uint8)).all(), col
 
 
+_TRAVEL = {}     # kind -> (frame, stats) of the scan from ordinary memory, page-locked in place: the reference of the other two ways
+
+
+@pytest.mark.parametrize("how", ["pageable", "pinned", "staged"])
+@pytest.mark.parametrize("kind", ["bed", "int8 C", "float64 C"])
+def test_scan_same_bits_however_X_travels(kind, how, monkeypatch):
+    """The association scan reads packed records, an int8 and a float64 matrix from ordinary memory (an array is page-locked in
+    place), from the caller's pinned memory, and through the workers' staging buffers where page-locking is refused: three batches,
+    the last ragged, n a multiple of neither 4 nor 64.  The same bytes reach the same kernels, so the six columns are equal as bit
+    patterns.  Records are always staged and never page-locked, so their two flags are False whichever way they come."""
+    from pygemma_amd import _lib, lmm, synth
+    from test_gpu_feed import pinned_copy, source
+    n, p, c = 333, 700, 3
+    monkeypatch.setattr(lmm, "_BATCH_SNPS", 256)
+    raw = synth.panel(n, p, c, seed=21)
+    X, _ = source(kind, n, p)
+
+    def scan(X):
+        st = {}
+        return lmm.pygemma(raw["Y"], X, raw["W"], raw["K"], stats=st), st
+
+    if kind not in _TRAVEL:
+        _TRAVEL[kind] = scan(X)
+    ref, st = _TRAVEL[kind]
+    if how == "pinned":
+        got, st = scan(pinned_copy(X))
+    elif how == "staged":
+        def refuse(arr, device=0):
+            raise _lib.PgError("registration refused (test)")
+        monkeypatch.setattr(_lib, "pin", refuse)
+        got, st = scan(X)
+    else:
+        got = ref
+    array = kind != "bed"
+    assert st["batches"] == 3
+    assert st["pinned_input"] is (array and how != "staged") and st["registered_in_place"] is (array and how == "pageable")
+    assert np.isfinite(got["F_wald"].to_numpy()).sum() > p // 2
+    for col in COLS:
+        a, b = got[col].to_numpy(), ref[col].to_numpy()
+        assert (a.view(np.uint8) == b.view(np.uint8)).all(), col
+
+
 def test_X_prefetched_during_the_eigendecomposition_same_bits(monkeypatch):
     """Opt-in (PYGEMMA_PREFETCH_MAX): with eigen=True from K, batches of a pinned C-contiguous X are copied to the device while the
     eigensolver runs and the SNP loop takes them from there; the rows are those of the run without prefetch, bit for bit."""

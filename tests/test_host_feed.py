@@ -72,3 +72,55 @@ def test_one_dtype_table_and_one_column_list():
     assert lmm._LM_COLS is ops.LM_COLS and not hasattr(ops, "_LM_DTYPES")
     assert lmm._Pinned is _feed._Pinned and lmm._put_window is _feed._put_window
     assert lmm._U_PANEL_BYTES == 256 << 20
+
+
+class _Recorder:
+    """Stands in for the loaded library: every entry point records (name, arguments) and succeeds."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def entry(*args):
+            self.calls.append((name, args))
+            return 0
+        return entry
+
+
+def test_one_bed_or_x_fork_passes_what_the_entry_points_take():
+    """_call_dev on the ragged last batch (SNPs [8, 10) of p = 10 at pb = 4, n = 13) of a PackedBed, a C-order and an F-order
+    array: for the three streamed consumers, the entry point's name and every argument in ABI order, written out."""
+    from pygemma_amd import _feed
+    n, p, s, e = 13, 10, 8, 10
+    H, SLOT, ACC, WORK, DC, DM, O = 0x10, 0x2000, 0x3000, 0x4000, 0x5000, 0x6000, (0x71, 0x72, 0x73, 0x74, 0x75)
+    c, t, std = 3, 2, 1
+    bed = _feed._describe(PackedBed(np.zeros((p, 4), np.uint8), n, count_A1=True))
+    xc = _feed._describe(np.zeros((n, p), np.float64))
+    xf = _feed._describe(np.zeros((n, p), np.float32, order="F"))
+    want = {
+        ("pg_kinship_{}_acc_dev", "bed"): ("pg_kinship_bed_acc_dev", (H, 13, 2, SLOT, 4, 1, 1, ACC)),
+        ("pg_kinship_{}_acc_dev", "C"): ("pg_kinship_x_acc_dev", (H, 13, 2, SLOT, 3, 2, 0, 1, ACC)),
+        ("pg_kinship_{}_acc_dev", "F"): ("pg_kinship_x_acc_dev", (H, 13, 2, SLOT, 2, 13, 1, 1, ACC)),
+        ("pg_lm_{}_dev", "bed"): ("pg_lm_bed_dev", (H, 13, 3, 2, 2, SLOT, 4, 1, WORK, 0x71, 0x72, 0x73, 0x74, 0x75, 10)),
+        ("pg_lm_{}_dev", "C"): ("pg_lm_x_dev", (H, 13, 3, 2, 2, SLOT, 3, 2, 0, WORK, 0x71, 0x72, 0x73, 0x74, 0x75, 10)),
+        ("pg_lm_{}_dev", "F"): ("pg_lm_x_dev", (H, 13, 3, 2, 2, SLOT, 2, 13, 1, WORK, 0x71, 0x72, 0x73, 0x74, 0x75, 10)),
+        ("pg_snp_stats_{}_dev", "bed"): ("pg_snp_stats_bed_dev", (H, 13, 2, SLOT, 4, 1, WORK, DC, DM)),
+        ("pg_snp_stats_{}_dev", "C"): ("pg_snp_stats_x_dev", (H, 13, 2, SLOT, 3, 2, 0, WORK, DC, DM)),
+        ("pg_snp_stats_{}_dev", "F"): ("pg_snp_stats_x_dev", (H, 13, 2, SLOT, 2, 13, 1, WORK, DC, DM)),
+    }
+    for kind, src in (("bed", bed), ("C", xc), ("F", xf)):
+        L = _Recorder()
+        _feed._call_dev(L, "pg_kinship_{}_acc_dev", src, (H, n, e - s), SLOT, e - s, (std, ACC))
+        _feed._call_dev(L, "pg_lm_{}_dev", src, (H, n, c, t, e - s), SLOT, e - s, (WORK, *O, p))
+        _feed._call_dev(L, "pg_snp_stats_{}_dev", src, (H, n, e - s), SLOT, e - s, (WORK, DC, DM))
+        assert L.calls == [want[stem, kind] for stem in ("pg_kinship_{}_acc_dev", "pg_lm_{}_dev", "pg_snp_stats_{}_dev")], kind
+        assert all(type(a) is int for _, args in L.calls for a in args), kind
+
+
+def test_a_failing_entry_point_is_reported_by_its_name(monkeypatch):
+    from pygemma_amd import _feed, _lib
+    seen = []
+    monkeypatch.setattr(_lib, "check", lambda rc, what="": seen.append((rc, what)))
+    L = _Recorder()
+    _feed._call_dev(L, "pg_lm_{}_dev", _feed._describe(np.zeros((5, 3), np.int8)), (1,), 2, 3, (4,))
+    assert seen == [(0, "pg_lm_x_dev")] and L.calls == [("pg_lm_x_dev", (1, 2, 0, 3, 0, 4))]
