@@ -244,6 +244,41 @@ int pg_snp_stats_x_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dt
                        double *moments);
 int pg_hwe_exact_dev(pg_ctx *ctx, int64_t n, int64_t p, const int64_t *counts, double *pval);
 
+/* ---- Linkage disequilibrium between hard-call SNPs on the int8 matrix pipe (csrc/ld.hip): the pairwise-complete Pearson r (PLINK's
+ * --r) that LD pruning, clumping and a region's LD matrix are made of.  Block conventions of pg_snp_stats_x_dev / pg_snp_stats_bed_dev.
+ * A SNP is hard-call when every non-missing value (in the element's own precision, nothing is rounded) is exactly 0, 1 or 2; missing is .bed code
+ * 01, NaN or +-Inf (an 8-bit block has no missing code); any other SNP counts as ALL missing.  With m_a[i] in {0, 1} "sample i is
+ * called" and x_a[i] its code (0 where missing), a pair (a, b) has six int32 sums over the n samples,
+ *     N = sum m_a m_b   Sa = sum x_a m_b   Sb = sum m_a x_b   Sab = sum x_a x_b   Saa = sum x_a^2 m_b   Sbb = sum m_a x_b^2
+ * then exactly in int64  ca = N Saa - Sa^2, cb = N Sbb - Sb^2, cab = N Sab - Sa Sb,  and
+ *     r = clamp((double)cab / sqrt((double)ca (double)cb), -1, 1)  rounded once to float32;  NaN when ca <= 0 or cb <= 0
+ * (no jointly called sample, or either SNP monomorphic among them).  A SNP against a copy gives exactly 1, against 2 - x exactly -1.
+ *   image   : pg_ld_image_bytes(n, pe) device bytes on a 16-byte boundary, opaque: int8 planes x, m, x^2 of pe SNP-major rows (n padded
+ *             with zeros to the K-tile of 128 samples) and per-SNP totals.  pg_ld_encode_{bed,x}_dev write the pb SNPs of a block to
+ *             the SNP positions [at, at + pb) of an image for pe; pg_ld_shift_dev moves SNPs [from, from + count) to [0, count) —
+ *             overlap-safe, the carry of a stream (4 ceil(count / from) device-to-device copies).  Positions never encoded hold whatever the memory held.
+ *   pg_ld_block_dev : r[ia ldr + ib] = r(a0 + ia of image A, b0 + ib of image B), ia < na, ib < nb (A and B may be the same image).
+ *   pg_ld_band_dev  : band[(j - j0) ldo + k] = r(j, j + 1 + k) for rows j in [j0, j0 + rows), k in [0, w), SNPs [0, have) of one image
+ *             encoded; a partner j + 1 + k >= have gives NaN.  Only the tiles that meet the band run.
+ *   sums    : or NULL; the six int32 of every pair, pair at element o of r / band at sums[6 o + t], t in the order N, Sa, Sb, Saa, Sbb,
+ *             Sab; zeros where the band has no partner.  Nothing outside the na x nb (rows x w) window of r and sums is written.
+ * A pair of 252-SNP tiles without a missing call takes one int8 product (N = n, the other sums from the per-SNP totals), any other
+ * nine products over the three planes: the same integers either way (PG_LD_PLANES=1 in the environment sends every tile the second
+ * way; tests and A/B timing only).
+ * PG_EINVAL for NULL pointers, an image off 16 bytes, n < 1, n >= 2^28 (every sum fits int32), negative counts, windows outside the
+ * image (at + pb > pe, a0 + na > pea, j0 + rows > have, have > pe, ...), w < 1 or strides too small; PG_ENOTSUP for an unknown dtype:
+ * a refused call enqueues nothing.  pg_ld_image_bytes is 0 for n or pe out of range (pe < 1, pe >= 2^31). */
+size_t pg_ld_image_bytes(int64_t n, int64_t pe);
+int pg_ld_encode_bed_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, void *image, int64_t pe,
+                         int64_t at);
+int pg_ld_encode_x_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, void *image, int64_t pe,
+                       int64_t at);
+int pg_ld_shift_dev(pg_ctx *ctx, int64_t n, void *image, int64_t pe, int64_t from, int64_t count);
+int pg_ld_block_dev(pg_ctx *ctx, int64_t n, const void *A, int64_t pea, int64_t a0, int64_t na, const void *B, int64_t peb, int64_t b0,
+                    int64_t nb, float *r, int64_t ldr, int *sums);
+int pg_ld_band_dev(pg_ctx *ctx, int64_t n, const void *image, int64_t pe, int64_t j0, int64_t rows, int64_t have, int64_t w, float *band,
+                   int64_t ldo, int *sums);
+
 /* ---- SNP-by-environment interaction (GEMMA's -gxe): for SNP g with rotated genotype x = U'x_g and rotated interaction
  * xe = U'(x_g o e), the REML Wald test of xe in  y ~ W' + x + xe,  W' = the c shared covariates (the caller's W and U'e).
  * Row g is by definition calculate(d, yr, [W', x], xe) of pg_assoc_dev's arithmetic with c + 1 covariates (decade scan,

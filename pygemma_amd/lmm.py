@@ -41,7 +41,7 @@ from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_re
 from . import model as _model
 
 __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
-           "kinship"] + _model.__all__
+           "kinship", "ld", "ld_window", "ld_prune", "clump"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -809,6 +809,293 @@ def snp_filter(st, maf=0.01, miss=0.05, hwe=0.0):
         pv = st["hwe_p"].to_numpy()
         keep &= (pv >= hwe) | np.isnan(pv)
     return keep
+
+
+# ---- linkage disequilibrium (csrc/ld.hip) ------------------------------------------------------------------------------------
+_LD_BATCH = 8192     # SNPs per batch of the LD streams by default: with the carry of `window` SNPs the image holds 3 n bytes per SNP
+
+
+def _ld_source(X, who):
+    X = _genotypes(X, who)
+    if X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError(f"{who} needs at least one sample and one SNP: X holds n={X.shape[0]}, p={X.shape[1]}")
+    return X
+
+
+def _ld_take(X, index):
+    """The SNPs `index` of a genotype source (a mask or integer indices, checked as PackedBed.take checks them; None: all of them) and
+    their columns in X: a PackedBed over the selected records, or the selected columns of an array."""
+    p = X.shape[1]
+    if index is None:
+        return X, np.arange(p, dtype=np.int64)
+    idx = np.asarray(index)
+    if idx.dtype == np.bool_:
+        if idx.shape != (p,):
+            raise ValueError(f"a mask over {p} SNPs has shape ({p},), not {idx.shape}")
+        idx = np.flatnonzero(idx)
+    else:
+        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+            raise ValueError("index must be a boolean mask of length p or a 1-D array of integer SNP indices")
+        idx = idx.astype(np.int64)
+        if idx.size and (idx.min() < -p or idx.max() >= p):
+            raise ValueError(f"SNP index out of range for {p} SNPs")
+        idx = np.where(idx < 0, idx + p, idx)
+    if idx.size < 1:
+        raise ValueError("the selection holds no SNP")
+    return (X.take(idx) if isinstance(X, PackedBed) else np.ascontiguousarray(X[:, idx])), idx
+
+
+def _check_unit(**kw):
+    for name, v in kw.items():
+        if not (isinstance(v, (int, float, np.integer, np.floating)) and 0 <= v <= 1):
+            raise ValueError(f"{name} must lie in [0, 1], not {v!r}")
+
+
+def _check_window(window):
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+        raise ValueError(f"window must be a positive integer, not {window!r}")
+
+
+def _ld_encode(L, ctx, src, pb, image, pe):
+    """All SNPs of `src` through the feed into positions [0, src.p) of an LD image for pe SNPs."""
+    with contextlib.closing(_Feed(ctx, src)) as feed:
+        for s, e, slot in feed.batches(pb):
+            _call_dev(L, "pg_ld_encode_{}_dev", src, (ctx.handle, src.n, e - s), slot, e - s, (image.ptr, pe, s))
+
+
+def ld(X, a=None, b=None, *, counts=False, device=0, stats=None):
+    """The LD matrix of a region: the float32 matrix r of shape (len(a), len(b)) of genotype correlations between the SNPs `a` and `b` of
+    X, each over the samples where both are called (the pairwise-complete Pearson r, PLINK's --r), for fine-mapping or a regional plot.
+
+    X (n, p): whatever snp_stats takes — a PackedBed, or an int8, uint8, float32 or float64 array in C or Fortran order, pinned or
+    pageable.  `a` and `b` are boolean masks of length p or integer indices, as for PackedBed.take; None is every SNP, and b=None is
+    b = a.  Only the selected SNPs are uploaded (through the two-slot feed), encoded into int8 planes on the device and multiplied on
+    the int8 matrix pipe (csrc/ld.hip).  Hard calls only: a SNP with an observed value other than 0, 1, 2 (a dosage, a centred column,
+    an int8 -1) counts as all missing; missing is .bed code 01, NaN or +-Inf.  From the six int32 sums of a pair
+      N = sum m_a m_b, Sa = sum x_a m_b, Sb = sum m_a x_b, Saa = sum x_a^2 m_b, Sbb = sum m_a x_b^2, Sab = sum x_a x_b
+      r = (N Sab - Sa Sb) / sqrt((N Saa - Sa^2)(N Sbb - Sb^2)), the products exact in int64, clamped to [-1, 1], one rounding to float32;
+    NaN when either variance is not positive (no jointly called sample, or a SNP monomorphic among them).  A copy of a SNP gives
+    exactly 1.0, its flip 2 - x exactly -1.0.  `counts=True` returns (r, sums) with the (len(a), len(b), 6) int32 sums in that order.
+    `stats` receives bytes_in and seconds.  Images and output that do not fit the device raise PgError.  Refused with ValueError before
+    any device work: X not 2-D or of another dtype, an empty X, a mask of another length, an index out of range, an empty selection."""
+    t0 = time.time()
+    X = _ld_source(X, "ld")
+    XA, ia = _ld_take(X, a)
+    XB, ib = (XA, ia) if b is None else _ld_take(X, b)
+    L = _lib.load()
+    _gpus()
+    sa, sb = _describe(XA), _describe(XB)
+    n, na, nb = sa.n, sa.p, sb.p
+    with _lib.Context(device) as ctx:
+        fixed = int(L.pg_ld_image_bytes(n, na)) + (0 if XB is XA else int(L.pg_ld_image_bytes(n, nb))) + na * nb * (28 if counts else 4)
+        pbs = [_fit_batch(ctx, None, _lm_batch(s), s.p, 128, lambda pb: fixed + 2 * pb * s.row_bytes, f"ld: n={n}, {na} x {nb} SNPs",
+                          "int8 images 3 n bytes per SNP, the r matrix, two batch slots") for s in (sa, sb)]
+        imA = ctx.alloc(L.pg_ld_image_bytes(n, na))
+        _ld_encode(L, ctx, sa, pbs[0], imA, na)
+        imB = imA
+        if XB is not XA:
+            imB = ctx.alloc(L.pg_ld_image_bytes(n, nb))
+            _ld_encode(L, ctx, sb, pbs[1], imB, nb)
+        dr = ctx.alloc(4 * na * nb)
+        ds = ctx.alloc(24 * na * nb) if counts else None
+        _lib.check(L.pg_ld_block_dev(ctx.handle, n, imA.ptr, na, 0, na, imB.ptr, nb, 0, nb, dr.ptr, nb, ds.ptr if counts else None), "pg_ld_block_dev")
+        ctx.sync()
+        r = dr.download((na, nb), np.float32)
+        sums = ds.download((na, nb, 6), np.int32) if counts else None
+    if stats is not None:
+        stats.update({"bytes_in": na * sa.row_bytes + (0 if XB is XA else nb * sb.row_bytes), "seconds": time.time() - t0})
+    return (r, sums) if counts else r
+
+
+def ld_window(X, window, *, snp_batch=None, device=0, verbose=0, stats=None):
+    """The LD band of X: the (p, window) float32 matrix band[j, k] = r(j, j + 1 + k), the correlation (as `ld` defines it) of every SNP
+    with its next `window` SNPs; NaN where j + 1 + k >= p.  What ld_prune and clump read.
+
+    X as for `ld`.  Streamed in SNP batches of `snp_batch` columns through the two-slot feed into ONE device image of snp_batch + window
+    SNPs: a batch is encoded behind the carry of the previous ones, the band rows whose whole window is present are computed (the last
+    batch computes the rest), and the last `window` SNPs move to the front; `window` may exceed `snp_batch`.  The band stays on the
+    device until one download at the end when it fits there, else it comes back batch by batch.  The result does not depend on the
+    batch boundaries, bit for bit (the sums are integers).  `stats` receives batches, bytes_in, seconds.  Refused with ValueError
+    before any device work: X not 2-D or of another dtype, an empty X, window < 1, a bad snp_batch."""
+    _check_snp_batch(snp_batch)
+    _check_window(window)
+    X = _ld_source(X, "ld_window")
+    L, t0 = _lib.load(), time.time()
+    src = _describe(X)
+    n, p, w = src.n, src.p, int(window)
+    _gpus()
+    out = None
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
+        free, _total = ctx.mem_info()
+        image_bytes = lambda pb: int(L.pg_ld_image_bytes(n, pb + w))
+        resident = 4 * p * w + image_bytes(128) + 2 * 128 * src.row_bytes <= 0.9 * free
+        out_bytes = (lambda pb: 4 * p * w) if resident else (lambda pb: 4 * (pb + w) * w)
+        pb = _fit_batch(ctx, snp_batch, min(_LD_BATCH, _lm_batch(src)), p, 128, lambda pb: out_bytes(pb) + image_bytes(pb) + 2 * pb * src.row_bytes,
+                        f"ld_window: n={n}, p={p}, window={w}", "the band or a batch of it, an int8 image of snp_batch + window SNPs, two batch slots")
+        pe = pb + w
+        image = ctx.alloc(image_bytes(pb))
+        dband = ctx.alloc(out_bytes(pb))
+        if not resident:
+            out = np.empty((p, w), np.float32)
+        base = have = emitted = 0          # the image holds SNPs [base, base + have); band rows [0, emitted) are computed
+        for s, e, slot in feed.batches(pb):
+            _call_dev(L, "pg_ld_encode_{}_dev", src, (ctx.handle, n, e - s), slot, e - s, (image.ptr, pe, have))
+            have += e - s
+            rows = (p if e == p else max(emitted, base + have - w)) - emitted
+            if rows > 0:
+                dst = dband.ptr + (4 * emitted * w if resident else 0)
+                _lib.check(L.pg_ld_band_dev(ctx.handle, n, image.ptr, pe, emitted - base, rows, have, w, dst, w, None), "pg_ld_band_dev")
+                if not resident:
+                    ctx.sync()
+                    out[emitted:emitted + rows] = dband.download((rows, w), np.float32)
+                emitted += rows
+            keep = base + have - emitted       # the SNPs whose rows are still to come: at most `window`
+            if e < p and have > keep:
+                _lib.check(L.pg_ld_shift_dev(ctx.handle, n, image.ptr, pe, have - keep, keep), "pg_ld_shift_dev")
+                base, have = base + have - keep, keep
+            _log(verbose - 1, f"ld_window: SNPs [{s},{e}) queued")
+        ctx.sync()
+        if resident:
+            out = dband.download((p, w), np.float32)
+    _stream_stats(stats, src, pb, t0)
+    _log(verbose, f"LD band: {p} SNPs x window {w} with {n} individuals in {time.time() - t0:.3f} s")
+    return out
+
+
+def _in_ld(r, r2):
+    """float64(r)^2 >= r2; a NaN pair is not in LD."""
+    with np.errstate(invalid="ignore"):
+        return np.asarray(r, np.float64) ** 2 >= r2
+
+
+def _prune_band(band, r2):
+    """The greedy forward pruning on a (p, window) band: SNP j stays unless a KEPT SNP i in [j - window, j) is in LD with it
+    (band[i, j - i - 1]^2 >= r2).  Pure NumPy; returns the boolean keep-mask."""
+    band = np.asarray(band)
+    p, w = band.shape
+    hit = _in_ld(band, r2)
+    keep = np.ones(p, bool)
+    for j in range(1, p):
+        i = np.arange(max(0, j - w), j)
+        keep[j] = not (keep[i] & hit[i, j - i - 1]).any()
+    return keep
+
+
+def ld_prune(X, window=50, r2=0.5, **stream_kw):
+    """LD pruning before lmm.kinship: a boolean keep-mask over the SNPs of X for PackedBed.take, X[:, keep] or kinship, so that no two
+    kept SNPs within `window` SNPs of each other have r^2 >= `r2`.  Greedy, front to back: SNP j is kept unless some KEPT SNP i in
+    [j - window, j) is in LD with it, r as `ld` defines it, float64(r)^2 >= r2, a NaN r never in LD.  The band comes from
+    ld_window(X, window, **stream_kw) (snp_batch, device, verbose, stats); the decision is the pure-NumPy _prune_band.
+    Against PLINK's --indep-pairwise window step r2: no minor-allele-frequency choice of which SNP of a pair goes (always the later
+    one), no step parameter (the window slides by one SNP), and every pair within the window is looked at once.  Monomorphic and
+    all-missing SNPs have no r and are KEPT: removing them is snp_filter's job.  Refused with ValueError before any device work: what
+    ld_window refuses, r2 outside [0, 1]."""
+    _check_unit(r2=r2)
+    return _prune_band(ld_window(X, window, **stream_kw), r2)
+
+
+def _signed(coord):
+    """Coordinates in a type whose differences have a sign: int64 for integers (an unsigned difference would wrap), float64 else."""
+    coord = np.asarray(coord)
+    return coord.astype(np.int64 if coord.dtype.kind in "iub" else np.float64)
+
+
+def _clump_reach(coord, run, window):
+    """Two pointers over candidates in column order: for candidate c the number of later candidates of its chromosome run within
+    `window` of it; the largest is the band width clumping needs."""
+    coord, m = _signed(coord), len(coord)
+    reach = np.zeros(m, np.int64)
+    hi = 0
+    for c in range(m):
+        hi = max(hi, c)
+        while hi + 1 < m and run[hi + 1] == run[c] and coord[hi + 1] - coord[c] <= window:
+            hi += 1
+        reach[c] = hi - c
+    return reach
+
+
+def _clump_band(band, pv, coord, run, p1, r2, window):
+    """The greedy clumping of m candidates (in column order) on their (m, w) band: by ascending p, ties by position, an unclumped
+    candidate with p <= p1 becomes an index SNP and takes every unclumped candidate of its chromosome run within `window` (in `coord`)
+    that is in LD with it.  Pure NumPy; returns [(index candidate, array of member candidates)] in the order the clumps were made."""
+    band, pv, coord, run = np.asarray(band), np.asarray(pv, np.float64), _signed(coord), np.asarray(run)
+    m, w = len(pv), band.shape[1] if band.ndim == 2 else 0
+    hit = _in_ld(band, r2) if w else np.zeros((m, 0), bool)
+    taken = np.zeros(m, bool)
+    out = []
+    for c in np.lexsort((np.arange(m), pv)):
+        if taken[c] or not pv[c] <= p1:
+            continue
+        taken[c] = True
+        lo = np.arange(max(0, c - w), c)
+        up = np.arange(c + 1, min(m, c + 1 + w))
+        near = np.concatenate([lo, up])
+        linked = np.concatenate([hit[lo, c - lo - 1], hit[c, up - c - 1]]) if w else np.zeros(0, bool)
+        ok = linked & ~taken[near] & (run[near] == run[c]) & (np.abs(coord[near] - coord[c]) <= window)
+        members = near[ok]
+        taken[members] = True
+        out.append((int(c), members.astype(np.int64)))
+    return out
+
+
+def clump(df, X, p1=1e-4, p2=1e-2, r2=0.5, window=250, col="p_wald", chrom=None, pos=None, **stream_kw):
+    """PLINK-style clumping of a scan frame into independent loci: df is the frame of a scan over the p SNPs of X (pygemma, pygemma_lm,
+    ...), `col` its p-value column.  Candidates are the rows with p < p2 (a NaN p is never one); only their SNPs are uploaded.  By
+    ascending p, ties by column, an unclumped candidate with p <= p1 becomes an index SNP and takes every unclumped candidate within
+    `window` that is in LD with it (r as `ld` defines it, float64(r)^2 >= r2, NaN never in LD).  Distance is |i - j| in columns of X,
+    or |pos_i - pos_j| when `pos` (length p, nondecreasing within a chromosome) is given; with `chrom` (length p, the SNPs of one
+    chromosome adjacent) a clump never crosses a change of chromosome.  The band width over the candidates is found on the host and
+    ld_window(candidates, width, **stream_kw) gives their r.
+    Returns a frame sorted by p, one row per clump: index (column of X), SNPs (when df has it), p, n_members, members (int64 array of
+    the columns of X the index SNP took, without itself).  The greedy is the pure-NumPy _clump_band.  Refused with ValueError before any
+    device work: what ld_window refuses, thresholds outside [0, 1], window < 1, `col` missing, lengths of df, chrom, pos that are not
+    p, pos decreasing within a chromosome."""
+    _check_unit(p1=p1, p2=p2, r2=r2)
+    if pos is None:
+        _check_window(window)
+    elif not (isinstance(window, (int, float, np.integer, np.floating)) and window >= 1):
+        raise ValueError(f"window must be at least 1, not {window!r}")
+    _check_snp_batch(stream_kw.get("snp_batch"))
+    X = _ld_source(X, "clump")
+    p = X.shape[1]
+    if col not in df:
+        raise ValueError(f"the frame has no column {col!r}")
+    pv = np.asarray(df[col], np.float64)
+    if pv.shape != (p,):
+        raise ValueError(f"shape mismatch: {len(pv)} rows of p-values for {p} SNPs")
+    run = np.zeros(p, np.int64)
+    if chrom is not None:
+        chrom = np.asarray(chrom)
+        if chrom.shape != (p,):
+            raise ValueError(f"shape mismatch: chrom has shape {chrom.shape} for {p} SNPs")
+        run[1:] = np.cumsum(chrom[1:] != chrom[:-1])
+    coord = np.arange(p, dtype=np.int64)
+    if pos is not None:
+        coord = np.asarray(pos)
+        if coord.shape != (p,) or coord.dtype.kind not in "iuf":
+            raise ValueError(f"shape mismatch: pos must be {p} numbers, got shape {coord.shape} of {coord.dtype}")
+        if coord.dtype.kind == "u" and coord.size and coord.max() > np.iinfo(np.int64).max:
+            raise ValueError("pos does not fit int64")
+        coord = _signed(coord)
+        if ((np.diff(coord) < 0) & (run[1:] == run[:-1])).any() or not np.isfinite(coord).all():
+            raise ValueError("pos must be finite and nondecreasing within a chromosome")
+    with np.errstate(invalid="ignore"):
+        cand = np.flatnonzero(pv < p2)
+    width = int(_clump_reach(coord[cand], run[cand], window).max()) if cand.size else 0
+    if width > 0:
+        band = ld_window(_ld_take(X, cand)[0], width, **stream_kw)
+    else:
+        band = np.zeros((cand.size, 0), np.float32)
+    clumps = _clump_band(band, pv[cand], coord[cand], run[cand], p1, r2, window)
+    clumps.sort(key=lambda cm: (pv[cand[cm[0]]], cm[0]))
+    out = {"index": np.array([cand[c] for c, _ in clumps], np.int64)}
+    if "SNPs" in df:
+        out["SNPs"] = np.asarray(df["SNPs"], object)[out["index"]]
+    out["p"] = pv[out["index"]]
+    out["n_members"] = np.array([len(mem) for _, mem in clumps], np.int64)
+    res = pd.DataFrame(out, columns=list(out))
+    res["members"] = pd.Series([cand[mem] for _, mem in clumps], dtype=object, index=res.index)
+    return res
 
 
 def _zkzt(L, Z, K):
