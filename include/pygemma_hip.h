@@ -279,6 +279,35 @@ int pg_ld_block_dev(pg_ctx *ctx, int64_t n, const void *A, int64_t pea, int64_t 
 int pg_ld_band_dev(pg_ctx *ctx, int64_t n, const void *image, int64_t pe, int64_t j0, int64_t rows, int64_t have, int64_t w, float *band,
                    int64_t ldo, int *sums);
 
+/* ---- Polygenic scores from RAW genotypes on the fp64 matrix pipe (csrc/prs.hip): S = G W, PLINK's --score, accumulated over
+ * the SNP batches of a stream.  Block conventions of pg_snp_stats_x_dev / pg_snp_stats_bed_dev: an (n x pb) sample-major (snp_major = 0,
+ * ldX >= pb) or (pb x n) SNP-major (ldX >= n) block of dtype PG_DTYPE_*, or pb packed .bed records (ldb >= ceil(n/4) bytes; code
+ * convention and count_a1 of pg_rotate_bed_dev).  An element is first rounded to float32; missing is .bed code 01 or a non-finite float
+ * element (an 8-bit block has no missing code); pad bits and pad elements are never read into a result.
+ *   Wt      : t <= PG_PRS_MAX_T weight columns, score-major: the weight of the block's SNP g in column k at Wt[k ldw + g], ldw >= pb.
+ *   score   : t rows of lds >= n doubles, called the same shape in int64 or NULL; both accumulated in place (the caller zeroes them
+ *             before the first batch); nothing outside [k lds, k lds + n) is written.
+ *   values  : x_gi = the stored value widened to fp64; a missing call is 0 (impute = 0) or mu_g (impute != 0), bit for bit the mean
+ *             pg_snp_stats_*_dev reports for the SNP (the exact division of a hard-call SNP, else the fixed-order two-pass mean: those
+ *             kernels run as a pre-pass over the batch); every call of an all-missing SNP is 0.
+ *             score[k][i] += sum_g x_gi w_gk;   called[k][i] += #{g : sample i called at g and w_gk != 0}, whatever impute.
+ *   order   : the block's SNPs are cut into chunks of PG_PRS_CHUNK from its first SNP; a chunk's partial is accumulated from zero on
+ *             v_mfma_f64_16x16x4_f64 (K = SNPs) in an order that depends only on the position inside the chunk; the partials are added
+ *             to score in ascending chunk order; no floating-point atomics.  A row depends only on the inputs and on where the batch
+ *             boundaries fall — not on pitches, alignment, the device or the run — and not on the batch sizes at all when every batch
+ *             but the last holds a multiple of PG_PRS_CHUNK SNPs.  The counts are exact.
+ *   work    : device scratch of pg_prs_work_bytes(n, pb, t) bytes: the pre-pass's outputs and the per-chunk partials (split-K: one
+ *             workgroup per chunk and 256 samples, 12 t n bytes per chunk, added in order by a second kernel); 0 for a refused shape.
+ * PG_EINVAL for NULL pointers (but called), n < 1, n >= 2^30, pb < 0, pb > 2^25, t < 1, a block of 2^31 or more workgroups
+ * (ceil(n / 256) sample groups x ceil(pb / 256) chunks), strides too small, or a pre-pass that pg_snp_stats_x_dev refuses; PG_ENOTSUP for t > PG_PRS_MAX_T or an unknown dtype: a refused call enqueues nothing.  pb = 0 is a no-op. */
+#define PG_PRS_CHUNK 256      /* SNPs per summation chunk */
+#define PG_PRS_MAX_T 64       /* weight columns per call: four 16-column tiles */
+size_t pg_prs_work_bytes(int64_t n, int64_t pb, int t);      /* 0 for a refused shape */
+int pg_prs_bed_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, int t, const double *Wt,
+                       int64_t ldw, int impute, void *work, double *score, int64_t *called, int64_t lds);
+int pg_prs_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, int t, const double *Wt,
+                     int64_t ldw, int impute, void *work, double *score, int64_t *called, int64_t lds);
+
 /* ---- SNP-by-environment interaction (GEMMA's -gxe): for SNP g with rotated genotype x = U'x_g and rotated interaction
  * xe = U'(x_g o e), the REML Wald test of xe in  y ~ W' + x + xe,  W' = the c shared covariates (the caller's W and U'e).
  * Row g is by definition calculate(d, yr, [W', x], xe) of pg_assoc_dev's arithmetic with c + 1 covariates (decade scan,

@@ -41,7 +41,7 @@ from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_re
 from . import model as _model
 
 __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
-           "kinship", "ld", "ld_window", "ld_prune", "clump"] + _model.__all__
+           "kinship", "ld", "ld_window", "ld_prune", "clump", "prs", "prs_weights"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -1096,6 +1096,153 @@ def clump(df, X, p1=1e-4, p2=1e-2, r2=0.5, window=250, col="p_wald", chrom=None,
     res = pd.DataFrame(out, columns=list(out))
     res["members"] = pd.Series([cand[mem] for _, mem in clumps], dtype=object, index=res.index)
     return res
+
+
+# ---- polygenic scores (csrc/prs.hip) -----------------------------------------------------------------------------------------
+_PRS_CHUNK = 256     # PG_PRS_CHUNK: batches are multiples of the summation chunk, so the bits do not depend on the batch size
+_PRS_MAX_T = 64      # PG_PRS_MAX_T: weight columns per kernel call
+_PRS_DROP = 0.5      # SNPs whose weights are all zero are dropped on the host when they are at least this share of the SNPs
+
+
+def _chunk_up(snps):
+    return -(-int(snps) // _PRS_CHUNK) * _PRS_CHUNK
+
+
+def _weight_columns(weights):
+    """(labels, (p, t) float64 array) of a weights argument: (p,), (p, t), a Series or a DataFrame (labelled by its columns, anything
+    else by 0..t-1)."""
+    if isinstance(weights, pd.DataFrame):
+        labels, Wm = list(weights.columns), weights.to_numpy()
+    else:
+        Wm = np.asarray(weights)
+        if Wm.ndim == 1:
+            Wm = Wm.reshape(-1, 1)
+        labels = list(range(Wm.shape[1])) if Wm.ndim == 2 else []
+    if Wm.ndim != 2:
+        raise ValueError(f"weights must be (p,) or (p, t), got shape {Wm.shape}")
+    try:
+        Wm = np.ascontiguousarray(Wm, np.float64)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"weights must be numbers: {exc}") from None
+    if Wm.shape[1] < 1:
+        raise ValueError("weights has no score column")
+    if not np.isfinite(Wm).all():
+        raise ValueError("weights must be finite: set the weight of a SNP that is not to count to 0")
+    return labels, Wm
+
+
+def prs(X, weights, *, missing="mean", counts=False, samples=None, device=0, snp_batch=None, verbose=0, stats=None):
+    """Polygenic scores S = G W (PLINK's --score; the clumping-and-thresholding score with prs_weights): the effect sizes of a scan
+    applied to a cohort, read once where its genotypes lie — no host decode of a .bed file, no float copy of X.
+
+    X (n, p): whatever snp_stats takes — a PackedBed, or an int8, uint8, float32 or float64 array in C or Fortran order, pinned or
+    pageable.  weights: (p,), (p, t), a Series or a DataFrame of finite numbers, cast to float64; a DataFrame's columns label the
+    scores, anything else is labelled 0..t-1.  Values are snp_stats' (float64 rounded to float32 per element; .bed code 01, NaN and
+    +-Inf are missing, an 8-bit array has no missing code).  missing="mean": a missing call takes the mean of the called genotypes
+    of its SNP in X — the very number snp_stats reports as `mean` — and every call of an all-missing SNP is 0; missing="skip": a
+    missing call is 0.  Returns a DataFrame of n rows (indexed by `samples` when given) with one float64 column per label,
+      S[i, k] = sum_g x_gi w_gk                                  in fp64 on the matrix pipe (csrc/prs.hip);
+    with counts=True a pair (scores, n_called), n_called[i, k] = #{g : sample i is called at g and w_gk != 0} as int64 in the same
+    shape (it does not depend on `missing`): PLINK's per-sample allele-count denominator, divided by two.
+    SNPs whose weights are all zero contribute nothing and are left on the host when they are at least half of the SNPs (PackedBed.take /
+    X[:, idx], as clump uploads only its candidates); when no SNP has a weight the result is zero and no device is touched.  The
+    rest streams through the two-slot feed in SNP batches; more than 64 weight columns run in groups of 64 over the same stream, so
+    X leaves the host once.  Sums run in chunks of 256 SNPs, added in order, and `snp_batch` (default: from n and the free device
+    memory) is rounded up to a multiple of 256: the returned bits do not depend on it, on the source's pitch or alignment, or on the run
+    (only on which SNPs are streamed).  `stats` receives batches, bytes_in, seconds and snps_used.  Refused with ValueError before any
+    device work: a non-finite weight, X not 2-D, of another dtype or empty, weights with other than p rows or without a column,
+    `samples` of another length, a bad snp_batch, `missing` other than "mean" or "skip"."""
+    _check_snp_batch(snp_batch)
+    if missing not in ("mean", "skip"):
+        raise ValueError(f'missing must be "mean" or "skip", not {missing!r}')
+    X = _genotypes(X, "prs")
+    n, p = X.shape
+    if n < 1 or p < 1:
+        raise ValueError(f"prs needs at least one sample and one SNP: X holds n={n}, p={p}")
+    labels, Wm = _weight_columns(weights)
+    if Wm.shape[0] != p:
+        raise ValueError(f"shape mismatch: {Wm.shape[0]} rows of weights for {p} SNPs")
+    if samples is not None and len(samples) != n:
+        raise ValueError(f"shape mismatch: {len(samples)} sample labels for {n} samples")
+    t, t0 = Wm.shape[1], time.time()
+    used = np.flatnonzero((Wm != 0).any(axis=1))
+    if used.size == 0:
+        S, Cn = np.zeros((t, n)), np.zeros((t, n), np.int64)
+        if stats is not None:
+            stats.update({"batches": 0, "bytes_in": 0, "seconds": time.time() - t0})
+    else:
+        if used.size <= (1 - _PRS_DROP) * p:
+            X, Wm = _ld_take(X, used)[0], Wm[used]
+        S, Cn = _prs_stream(X, np.ascontiguousarray(Wm.T), missing == "mean", bool(counts), device, snp_batch, verbose, stats)
+    if stats is not None:
+        stats["snps_used"] = int(X.shape[1]) if used.size else 0
+    index = None if samples is None else pd.Index(samples)
+    scores = pd.DataFrame(S.T, columns=labels, index=index)
+    return (scores, pd.DataFrame(Cn.T, columns=labels, index=index)) if counts else scores
+
+
+def _prs_stream(X, Wt, impute, counts, device, snp_batch, verbose, stats):
+    """The streamed score: the (t, p) score-major weights uploaded once, then SNP batches from the feed (_feed._Feed) through
+    pg_prs_{bed,x}_acc_dev — every group of 64 weight columns on each batch before the next is taken — into (t, n) accumulators on
+    the device.  Returns the host arrays (scores, counts or None)."""
+    L, t0 = _lib.load(), time.time()
+    src = _describe(X)
+    n, p = src.n, src.p
+    t = Wt.shape[0]
+    tg = min(t, _PRS_MAX_T)
+    _gpus()
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
+        fixed = 8 * t * p + (16 if counts else 8) * t * n
+        pb = _fit_batch(ctx, None if snp_batch is None else _chunk_up(snp_batch), _chunk_up(_lm_batch(src)), p, _PRS_CHUNK,
+                        lambda pb: fixed + 2 * pb * src.row_bytes + int(L.pg_prs_work_bytes(n, pb, tg)),
+                        f"prs: n={n}, p={p}, t={t}", "weights, score rows, two batch slots, the pre-pass and the chunk partials")
+        if pb < p:
+            pb = max(_PRS_CHUNK, pb // _PRS_CHUNK * _PRS_CHUNK)
+        dW = ctx.to_device(Wt)
+        work = ctx.alloc(L.pg_prs_work_bytes(n, pb, tg))
+        dS, dC = ctx.alloc(8 * t * n), ctx.alloc(8 * t * n) if counts else None
+        for buf in (dS, dC):
+            if buf is not None:
+                _lib.check(L.pg_memset(ctx.handle, buf.ptr, 0, 8 * t * n), "pg_memset")
+        for s, e, slot in feed.batches(pb):
+            for k0 in range(0, t, _PRS_MAX_T):
+                tk = min(_PRS_MAX_T, t - k0)
+                _call_dev(L, "pg_prs_{}_acc_dev", src, (ctx.handle, n, e - s), slot, e - s,
+                          (tk, dW.ptr + 8 * (k0 * p + s), p, int(impute), work.ptr, dS.ptr + 8 * k0 * n, dC.ptr + 8 * k0 * n if counts else None, n))
+            _log(verbose - 1, f"prs: SNPs [{s},{e}) queued")
+        ctx.sync()
+        out = dS.download((t, n), np.float64), dC.download((t, n), np.int64) if counts else None
+    _stream_stats(stats, src, pb, t0)
+    _log(verbose, f"Polygenic scores: {p} SNPs x {t} score(s) for {n} individuals in {time.time() - t0:.3f} s")
+    return out
+
+
+def prs_weights(df, loci=None, thresholds=(5e-8, 1e-5, 1e-3, 1e-2, 0.05, 1.0), col="p_wald", beta="beta"):
+    """The weights of a clumping-and-thresholding score (PRSice's C+T) from a scan frame; pure NumPy.  df: the frame of a scan over p
+    SNPs with its p-value column `col` and effect column `beta`; loci: the frame clump(df, X) returned, or None for no clumping.
+    Returns a (p, t) float64 DataFrame with one column per threshold, labelled by it: column k holds beta_g where p_g <= thresholds[k]
+    (equality counts), p_g and beta_g are finite and — with loci — g is one of loci["index"]; 0 elsewhere.  Hand it to prs.  ValueError:
+    a missing column, a threshold outside [0, 1], an index outside the frame."""
+    for name in (col, beta):
+        if name not in df:
+            raise ValueError(f"the frame has no column {name!r}")
+    thresholds = list(thresholds)
+    _check_unit(**{f"thresholds[{k}]": v for k, v in enumerate(thresholds)})
+    pv, b = np.asarray(df[col], np.float64), np.asarray(df[beta], np.float64)
+    p = len(pv)
+    keep = np.isfinite(pv) & np.isfinite(b)
+    if loci is not None:
+        if "index" not in loci:
+            raise ValueError("loci has no column 'index': it is not a frame of clump")
+        idx = np.asarray(loci["index"])
+        if idx.size and (idx.dtype.kind not in "iu" or idx.min() < 0 or idx.max() >= p):
+            raise ValueError(f"loci holds an index outside the frame's {p} SNPs")
+        index = np.zeros(p, bool)
+        index[idx.astype(np.int64)] = True
+        keep &= index
+    with np.errstate(invalid="ignore"):
+        cols = [np.where(keep & (pv <= thr), b, 0.0) for thr in thresholds]
+    return pd.DataFrame(np.stack(cols, axis=1) if cols else np.zeros((p, 0)), columns=list(thresholds), index=df.index)
 
 
 def _zkzt(L, Z, K):
