@@ -368,6 +368,11 @@ int pg_rotate_dev(pg_ctx *ctx, int64_t n, int64_t p, const float *U, int64_t ldU
  *                        or Inf (call pg_rotate_dev: its propagation is the reference's).  Synchronises the stream. */
 size_t pg_geno_prep_bytes(int64_t n);
 size_t pg_geno_work_bytes(int64_t n, int64_t p);
+/* The detect pass in front of these rotations reads X ONCE (extremes, codes and flags from one kernel, 2-bit tags of every element of
+ * a 32-SNP strip held in LDS) when n <= pg_geno_onepass_max_n(LDS bytes one workgroup may use), and in two passes above that;
+ * pg_geno_onepass_limit is that bound on the context's device.  Same outputs either way; PG_GENO_ONEPASS=0 forces the two passes. */
+int64_t pg_geno_onepass_max_n(int64_t lds_bytes);
+int64_t pg_geno_onepass_limit(pg_ctx *ctx);
 int pg_geno_prep_dev(pg_ctx *ctx, int64_t n, const float *U, int64_t ldU, void *Uprep);
 int pg_rotate_geno_dev(pg_ctx *ctx, int64_t n, int64_t p, const void *Uprep, const float *X_n_by_p, int64_t ldX, float *Xr,
                        int64_t ldx, void *work, int *is_geno);

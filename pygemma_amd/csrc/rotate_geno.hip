@@ -29,10 +29,12 @@ namespace pg {
 // Device-side choice of the rotation path (pg_rotate_auto_dev): every candidate kernel of a block is enqueued and looks at the
 // flags the detect pass left — flag[0] bit 0: not genotype-valued, bit 1: NaN/Inf present; flag[1]: some column has an imputed
 // value — so the host never waits for them.
-enum { COND_ALWAYS = 0, COND_PASS1 = 1, COND_PASS2 = 2, COND_INDICATOR = 3, COND_SPLIT = 4, COND_FP32 = 5, COND_GENO = 6 };
+// flag[2] (one-pass detect: detect_encode_kernel): some column has to be encoded again by encode_geno_kernel.
+enum { COND_ALWAYS = 0, COND_PASS1 = 1, COND_PASS2 = 2, COND_INDICATOR = 3, COND_SPLIT = 4, COND_FP32 = 5, COND_GENO = 6, COND_ENCODE = 7 };
 __device__ __forceinline__ bool run_cond(const int *flag, int mode)
 {
     if (!flag || mode == COND_ALWAYS) return true;
+    if (mode == COND_ENCODE) return flag[2] != 0;
     const int f0 = flag[0], f1 = flag[1];
     switch (mode) {
         case COND_PASS1: return !(f0 & 2);
@@ -160,12 +162,15 @@ __global__ __launch_bounds__(256) void minmax_geno_kernel(long long n, long long
 }
 template <class T, bool I8 = false>      // I8: the codes as int8 0/1/2 with row stride ldk BYTES (the int8 kernel's operand), else fp16 0.0/1.0/2.0
 __global__ __launch_bounds__(256) void encode_geno_kernel(long long n, long long p, const T *X, long long ldX, const int *kmin, const int *kmax,
-                                                          int *other, unsigned short *Gt, long long ldk, int *flag)
+                                                          int *other, unsigned short *Gt, long long ldk, int *flag, const int *cond = nullptr)
 {
     // tile: 64 SNPs x 128 samples — 256-byte row segments on the way in (64 floats) and on the way out (128 fp16 codes)
     __shared__ unsigned short tile[128][66];
-    const long long g0 = (long long)blockIdx.x * 64, i0 = (long long)blockIdx.y * 128;
+    if (!run_cond(cond, COND_ENCODE)) return;
+    const long long tiles_g = (p + 63) / 64, tiles = tiles_g * ((ldk + 127) / 128);
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x, __syncthreads()) {      // bounded grid (tile_grid): column tiles fastest, as a 2-D grid dispatches
+    const long long g0 = (t % tiles_g) * 64, i0 = (t / tiles_g) * 128;
     const long long g = g0 + tx;
     const float lo = (g < p) ? key2f(kmin[g]) : 0.0f, hv = (g < p) ? key2f(kmax[g]) : 0.0f;
     const float mid = lo + 0.5f * (hv - lo), tol = 8.0f * 1.1920929e-7f * fmaxf(fabsf(lo), fabsf(hv));
@@ -199,6 +204,160 @@ __global__ __launch_bounds__(256) void encode_geno_kernel(long long n, long long
             else *reinterpret_cast<unsigned *>(Gt + gg * ldk + i) = (unsigned)tile[2 * tx][r] | ((unsigned)tile[2 * tx + 1][r] << 16);
         }
     }
+    }
+}
+
+// minmax + encode in ONE read of the block (n small enough for the tags below to fit the LDS: onepass_lds_bytes).  A 1024-thread
+// workgroup owns a strip of 32 SNP columns and walks all n rows once, 32 rows (128-byte segments of float32 X) per sweep and 16 sweeps
+// of loads in flight per thread; strips follow the workgroup index, so the ~256 resident workgroups ask for neighbouring segments of
+// the same rows at about the same time.  What a value will be encoded as is only known once the column's extremes are, so each
+// element leaves a 2-bit TAG in LDS: the index of its bit pattern in a per-column dictionary of up to four patterns, filled in
+// first-come order by LDS compare-and-swap (slot s is tried before s + 1 and never changes once set, so a pattern's tag does not
+// depend on who inserted it; the ORDER of the slots is a race, the codes that come out are not).  After the last row lane c of wave 0
+// classifies the dictionary of column c by encode_geno_kernel's rules — the same float32 expressions, on the same values — and the
+// workgroup maps tags to codes and writes its 32 SNP-major rows of Gt whole.  kmin / kmax / other / flag[0..1] are what
+// minmax_geno_kernel + encode_geno_kernel leave.  A column with a fifth pattern stops tagging (it still feeds the extremes); unless
+// its four entries already hold two `other` values (the block is then no genotype block: dosages end here), and for any block with
+// a NaN / Inf, flag[2] asks for encode_geno_kernel, which then runs as it always did, on these extremes.
+// Tag word of thread (rr = tid / 32, c = tid % 32), layer j: rows 512 j + rr + 32 k, k = 0 .. 15, at bits 2k; stored at
+// [j][c][rr] with 33 words per column: the write-out reads 16 (int8) or 8 (fp16) consecutive rr of one column per lane.
+// Measured (profiles/geno_prepass_bench.json; n = 10 000, 100 000 standardised SNPs, parent and this build alternated three times on
+// one MI355X): this kernel 1.14 ms for 4 GB read + 1 GB written (4.4 TB/s; minmax 0.79 + encode 1.58 + two predicated-off grid walks
+// 0.23 before: 2.62 -> 1.16 ms of pre-pass per step), rotation stage 23.48 -> 21.87 ms (the parent's own runs lie within 0.06 ms),
+// bench step 54.19 -> 52.69 ms; with int8 X 54.05 -> 52.51 ms (kernel 0.99 ms); a 16 384-SNP dosage block (every column proves
+// itself no genotype column from its first four patterns, so encode_geno_kernel never runs) 19.10 -> 16.50 ms; the fp32 fallback
+// unchanged (186.1 / 186.2 ms).  Outputs byte-equal to the parent's.  The first form of the write-out (shift / mask / select per
+// code, ~10 VALU each) took 1.30 ms: the workgroup is alone on its CU, so nothing loads while it writes; now one v_perm_b32 per four codes.
+constexpr int OP_COLS = 32, OP_THREADS = 1024, OP_SWEEP = OP_THREADS / OP_COLS, OP_LAYER_ROWS = 16 * OP_SWEEP;
+constexpr int OP_LAYER_WORDS = OP_COLS * (OP_SWEEP + 1), OP_FIXED_WORDS = 8 * OP_COLS;      // fixed: dictionary [32][4], min key, max key, state, code map
+template <class T, bool I8>
+__global__ __launch_bounds__(OP_THREADS) void detect_encode_kernel(long long n, long long p, const T *X, long long ldX, int *kmin, int *kmax, int *other,
+                                                                   unsigned short *Gt, long long ldk, int *flag)
+{
+    extern __shared__ int op_lds[];
+    int *const dict = op_lds, *const cmin = op_lds + 4 * OP_COLS, *const cmax = cmin + OP_COLS, *const cstate = cmax + OP_COLS, *const cmap = cstate + OP_COLS;
+    unsigned *const tags = reinterpret_cast<unsigned *>(op_lds + OP_FIXED_WORDS);
+    const int tid = threadIdx.x, c = tid & (OP_COLS - 1), rr = tid >> 5;
+    // 1-byte X: a row segment of a strip is 32 bytes, so the four strips of a 128-byte line go to ONE XCD (workgroup b runs on XCD b % 8)
+    long long strip = blockIdx.x;
+    if (sizeof(T) == 1 && (strip | 31) < (long long)gridDim.x) strip = (strip & ~31LL) + 4 * (strip & 7) + ((strip >> 3) & 3);
+    const long long g = strip * OP_COLS + c;
+    const bool live = g < p;
+    if (tid < 4 * OP_COLS) dict[tid] = OTHER_EMPTY;
+    if (tid < OP_COLS) { cmin[tid] = 0x7FFFFFFF; cmax[tid] = (int)0x80000000; cstate[tid] = 0; cmap[tid] = 0; }
+    __syncthreads();
+    const T *xp = X + (live ? g : 0);
+    volatile int *const dc = dict + 4 * c;
+    int d0 = OTHER_EMPTY, d1 = OTHER_EMPTY, d2 = OTHER_EMPTY, d3 = OTHER_EMPTY;      // this thread's view of its column's dictionary
+    bool full = !live;                                                               // the column met a fifth pattern (or is past p): no tags
+    int lo = 0x7FFFFFFF, hi = (int)0x80000000;
+    const int layers = (int)((n + OP_LAYER_ROWS - 1) / OP_LAYER_ROWS);
+    for (int j = 0; j < layers; j++) {
+        float x[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) {      // rows past n repeat row n - 1: no new value, and the write-out zeroes their codes
+            long long i = (long long)j * OP_LAYER_ROWS + rr + OP_SWEEP * k;
+            i = i < n ? i : n - 1;
+            x[k] = (float)xp[i * ldX];
+        }
+        unsigned w = 0;
+        const bool tagging = __builtin_amdgcn_ballot_w64(!full) != 0;      // wave-uniform
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const int xb = __float_as_int(x[k]), key = f2key(x[k]);
+            lo = key < lo ? key : lo; hi = key > hi ? key : hi;
+            if (!tagging) continue;
+            int t = xb == d1 ? 1 : 0;
+            t = xb == d2 ? 2 : t;
+            t = xb == d3 ? 3 : t;
+            if (!(xb == d0 || t != 0 || full)) {      // not in this thread's view: insert it, or find it where another thread did
+                t = 4;
+                for (int s = 0; s < 4 && t == 4; s++) {
+                    const int prev = atomicCAS(dict + 4 * c + s, OTHER_EMPTY, xb);
+                    if (prev == OTHER_EMPTY || prev == xb) t = s;
+                }
+                d0 = dc[0]; d1 = dc[1]; d2 = dc[2]; d3 = dc[3];
+                if (t == 4) { full = true; cstate[c] = 1; t = 0; }
+            }
+            w |= (unsigned)t << (2 * k);
+        }
+        tags[j * OP_LAYER_WORDS + c * (OP_SWEEP + 1) + rr] = w;
+    }
+    if (live) { atomicMin(&cmin[c], lo); atomicMax(&cmax[c], hi); }
+    __syncthreads();
+    if (tid < OP_COLS) {      // wave 0, lane c: column c
+        bool nonfinite = false, bad = false, any_ind = false, again = false;
+        if (live) {
+            const int kl = cmin[c], kh = cmax[c];
+            kmin[g] = kl; kmax[g] = kh;
+            const float lov = key2f(kl), hv = key2f(kh);
+            nonfinite = !(fabsf(lov) <= 3.0e38f) || !(fabsf(hv) <= 3.0e38f);      // the order of the keys puts every NaN / Inf at an end
+            const float mid = lov + 0.5f * (hv - lov), tol = 8.0f * 1.1920929e-7f * fmaxf(fabsf(lov), fabsf(hv));
+            int cm = 0, oth = OTHER_EMPTY;
+            for (int s = 0; s < 4; s++) {
+                const int e = dict[4 * c + s];
+                if (e == OTHER_EMPTY) break;
+                const float xv = __int_as_float(e);
+                if (xv == lov) { }
+                else if (xv == hv) cm |= 2 << (2 * s);
+                else if (fabsf(xv - mid) <= tol) cm |= 1 << (2 * s);
+                else {
+                    if (oth == OTHER_EMPTY) oth = e;
+                    else if (oth != e) bad = true;
+                    any_ind = true;
+                }
+            }
+            // a full dictionary settles the column only when it already disqualifies the block; with a NaN / Inf about, encode_geno_kernel decides
+            again = nonfinite || (cstate[c] != 0 && !bad);
+            if (again) { oth = OTHER_EMPTY; bad = false; any_ind = false; }
+            other[g] = oth;
+            cmap[c] = cm;
+            if (again || cstate[c] != 0) cstate[c] = 2;      // no codes to write
+        }
+        if (__builtin_amdgcn_ballot_w64(nonfinite) != 0 && tid == 0) atomicOr(flag, 2);
+        if (__builtin_amdgcn_ballot_w64(bad) != 0 && tid == 0) atomicOr(flag, 1);
+        if (__builtin_amdgcn_ballot_w64(any_ind) != 0 && tid == 0) atomicOr(flag + 1, 1);
+        if (__builtin_amdgcn_ballot_w64(again) != 0 && tid == 0) atomicOr(flag + 2, 1);
+    }
+    __syncthreads();
+    // write-out: wave w takes columns 2w and 2w + 1, a lane 16 bytes of the row at a time (ldk is a multiple of 64 elements)
+    constexpr int E = I8 ? 16 : 8;
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int col = 2 * wave; col < 2 * wave + 2; col++) {
+        const long long gg = strip * OP_COLS + col;
+        if (gg >= p || cstate[col] == 2) continue;
+        const unsigned cm = (unsigned)cmap[col];
+        const unsigned lut = (cm & 3) | ((cm >> 2) & 3) << 8 | ((cm >> 4) & 3) << 16 | ((cm >> 6) & 3) << 24;      // the code of tag t in byte t
+        unsigned char *row = reinterpret_cast<unsigned char *>(Gt) + gg * ldk * (I8 ? 1 : 2);
+        for (long long i0 = (long long)lane * E; i0 < ldk; i0 += 64 * E) {
+            const int kk = (int)(i0 >> 5), sh = 2 * (kk & 15);
+            const unsigned *tw = tags + (kk >> 4) * OP_LAYER_WORDS + col * (OP_SWEEP + 1) + (int)(i0 & 31);
+            unsigned out[4] = {0, 0, 0, 0};
+            if (I8) {      // four tags -> a byte selector -> four codes in one v_perm_b32 (both sources the table: selectors 0 .. 3 and 4 .. 7 alike)
+#pragma unroll
+                for (int e = 0; e < E; e++) out[e >> 2] |= ((tw[e] >> sh) & 3) << (8 * (e & 3));
+#pragma unroll
+                for (int q = 0; q < 4; q++) out[q] = __builtin_amdgcn_perm(lut, lut, out[q]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < E; e++) {
+                    const unsigned code = (cm >> (2 * ((tw[e] >> sh) & 3))) & 3;
+                    out[e >> 1] |= (code == 0 ? 0u : (code == 1 ? 0x3C00u : 0x4000u)) << (16 * (e & 1));
+                }
+            }
+            if (i0 + E > n) {      // the pad of the row: zero codes
+#pragma unroll
+                for (int e = 0; e < E; e++)
+                    if (i0 + e >= n) out[I8 ? e >> 2 : e >> 1] &= I8 ? ~(0xFFu << (8 * (e & 3))) : ~(0xFFFFu << (16 * (e & 1)));
+            }
+            *reinterpret_cast<uint4 *>(row + i0 * (I8 ? 1 : 2)) = make_uint4(out[0], out[1], out[2], out[3]);
+        }
+    }
+}
+// LDS of detect_encode_kernel at n samples, and the largest n that fits lds_bytes (what the host decides the path from)
+static size_t onepass_lds_bytes(long long n)
+{
+    return 4 * ((size_t)((n + OP_LAYER_ROWS - 1) / OP_LAYER_ROWS) * OP_LAYER_WORDS + OP_FIXED_WORDS);
 }
 
 // general float columns: s x = X1 + X2 (two fp16 planes, round to nearest twice), s = the power of two that puts the
@@ -218,8 +377,10 @@ __global__ __launch_bounds__(256) void split_x_kernel(long long n, long long p, 
 {
     __shared__ unsigned short t1[128][66], t2[128][66];
     if (!run_cond(cond, COND_SPLIT)) return;
-    const long long g0 = (long long)blockIdx.x * 64, i0 = (long long)blockIdx.y * 128;
+    const long long tiles_g = (p + 63) / 64, tiles = tiles_g * ((ldk + 127) / 128);
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x, __syncthreads()) {      // bounded grid (tile_grid)
+    const long long g0 = (t % tiles_g) * 64, i0 = (t / tiles_g) * 128;
     const long long g = g0 + tx;
     const float sc = (g < p) ? split_scale(key2f(kmin[g]), key2f(kmax[g])) : 1.0f;
 #pragma unroll 8
@@ -241,6 +402,7 @@ __global__ __launch_bounds__(256) void split_x_kernel(long long n, long long p, 
             *reinterpret_cast<unsigned *>(X2 + gg * ldk + i) = (unsigned)t2[2 * tx][r] | ((unsigned)t2[2 * tx + 1][r] << 16);
         }
     }
+    }
 }
 __global__ void params_split_kernel(long long p, const int *kmin, const int *kmax, float *v0, float *dx, float *dlt, const int *cond = nullptr)
 {
@@ -257,8 +419,10 @@ __global__ __launch_bounds__(256) void indicator_geno_kernel(long long n, long l
 {
     __shared__ unsigned short tile[32][34];
     if (!run_cond(cond, COND_INDICATOR)) return;
-    const long long g0 = (long long)blockIdx.x * 32, i0 = (long long)blockIdx.y * 32;
+    const long long tiles_g = (p + 31) / 32, tiles = tiles_g * ((ldk + 31) / 32);
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x, __syncthreads()) {      // bounded grid (tile_grid)
+    const long long g0 = (t % tiles_g) * 32, i0 = (t / tiles_g) * 32;
     const long long g = g0 + tx;
     const int ob = (g < p) ? other[g] : OTHER_EMPTY;
     for (int r = ty; r < 32; r += 8) {
@@ -272,6 +436,7 @@ __global__ __launch_bounds__(256) void indicator_geno_kernel(long long n, long l
             if (I8) reinterpret_cast<signed char *>(Gi)[gg * ldk + i] = (signed char)tile[tx][r];
             else Gi[gg * ldk + i] = tile[tx][r];
         }
+    }
     }
 }
 __global__ void params_geno_kernel(long long p, const int *kmin, const int *kmax, const int *other, float *v0, float *dx, float *dlt)
@@ -1073,6 +1238,60 @@ extern "C" size_t pg_geno_work_bytes(int64_t n, int64_t p)
     const long long ldk = (n + GBK - 1) / GBK * GBK;
     return 2 * (((size_t)p * ldk * 2 + 255) & ~(size_t)255) + (size_t)p * 24 + 512;   // codes, indicator plane, v0/dx/delta/min/max/other
 }
+// Largest n whose tags fit lds_bytes of LDS (0: none); a plain function of the limit, so the choice of path can be checked anywhere.
+extern "C" int64_t pg_geno_onepass_max_n(int64_t lds_bytes)
+{
+    const long long layers = (lds_bytes / 4 - OP_FIXED_WORDS) / OP_LAYER_WORDS;
+    return layers > 0 ? layers * OP_LAYER_ROWS : 0;
+}
+// ... and on this context's device: the limit is the LDS one workgroup may ask for (detect_encode_kernel runs one per CU)
+extern "C" int64_t pg_geno_onepass_limit(pg_ctx *ctx)
+{
+    int lds = 0;
+    if (!ctx || hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) return 0;
+    return pg_geno_onepass_max_n(lds);
+}
+// PG_GENO_ONEPASS=0 keeps the two-pass detect (A/B, tests); read per call
+static bool geno_onepass_enabled()
+{
+    const char *e = getenv("PG_GENO_ONEPASS");
+    return !(e && atoi(e) == 0);
+}
+// Workgroups of a tile-loop kernel (encode / indicator / split): a few per CU, so a launch whose condition is false costs a launch
+static unsigned tile_grid(const pg_ctx *ctx, long long tiles_x, long long tiles_y)
+{
+    const long long tiles = tiles_x * tiles_y, cap = 8LL * ctx->num_cu;
+    return (unsigned)(tiles < cap ? tiles : cap);
+}
+
+// The detect pass of a block: kmin / kmax / other, the codes Gt (int8 with row stride ldk8 when i8, else fp16 with ldk), v0 / dx / dlt
+// and flag[0..1]; flag[2] is the one-pass kernel's request for encode_geno_kernel.  Nothing synchronises.
+template <class T>
+static int launch_detect(pg_ctx *ctx, long long n, long long p, const T *X, long long ldX, int *kmin, int *kmax, int *other, unsigned short *Gt,
+                         long long ldk, long long ldk8, bool i8, float *v0, float *dx, float *dlt, int *flag)
+{
+    PG_HIP(hipMemsetAsync(flag, 0, 12, ctx->stream));
+    const long long ld = i8 ? ldk8 : ldk;
+    const unsigned egrid = tile_grid(ctx, (p + 63) / 64, (ld + 127) / 128);
+    if (geno_onepass_enabled() && n <= pg_geno_onepass_limit(ctx)) {
+        const size_t lds = onepass_lds_bytes(n);
+        const unsigned strips = (unsigned)((p + OP_COLS - 1) / OP_COLS);
+        auto kern = i8 ? &detect_encode_kernel<T, true> : &detect_encode_kernel<T, false>;
+        PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        kern<<<strips, OP_THREADS, lds, ctx->stream>>>(n, p, X, ldX, kmin, kmax, other, Gt, ld, flag);
+        if (i8) encode_geno_kernel<T, true><<<egrid, 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, other, Gt, ld, flag, flag);
+        else encode_geno_kernel<T><<<egrid, 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, other, Gt, ld, flag, flag);
+    } else {
+        minmax_init_kernel<<<(unsigned)((p + 255) / 256), 256, 0, ctx->stream>>>(p, kmin, kmax, other);
+        minmax_geno_kernel<T><<<dim3((unsigned)((p + 63) / 64), (unsigned)((n + 255) / 256)), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, flag);
+        if (i8) encode_geno_kernel<T, true><<<egrid, 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, other, Gt, ld, flag);
+        else encode_geno_kernel<T><<<egrid, 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, other, Gt, ld, flag);
+    }
+    params_geno_kernel<<<(unsigned)((p + 255) / 256), 256, 0, ctx->stream>>>(p, kmin, kmax, other, v0, dx, dlt);
+    PG_HIP(hipGetLastError());
+    return PG_OK;
+}
+
 template <class T>
 static int rotate_geno_any(pg_ctx *ctx, int64_t n, int64_t p, const void *Uprep, const T *X, int64_t ldX, float *Xr, int64_t ldx,
                            void *work, int *is_geno_host)
@@ -1086,31 +1305,26 @@ static int rotate_geno_any(pg_ctx *ctx, int64_t n, int64_t p, const void *Uprep,
     char *tail = (char *)work + 2 * plane;
     float *v0 = (float *)tail, *dx = v0 + p, *dlt = dx + p;
     int *kmin = (int *)(dlt + p), *kmax = kmin + p, *other = kmax + p;
-    int *flag = other + p;           // flag[0]: not a genotype block; flag[1]: some column holds an other (imputed) value
-    PG_HIP(hipMemsetAsync(flag, 0, 8, ctx->stream));
-    minmax_init_kernel<<<(unsigned)((p + 255) / 256), 256, 0, ctx->stream>>>(p, kmin, kmax, other);
-    minmax_geno_kernel<T><<<dim3((unsigned)((p + 63) / 64), (unsigned)((n + 255) / 256)), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, flag);
+    int *flag = other + p;           // flag[0]: not a genotype block; flag[1]: some column holds an other (imputed) value; flag[2]: see launch_detect
     const bool i8 = geno_i8_enabled();
     const long long ldk8 = prep_layout(n).ldk8;
-    if (i8) encode_geno_kernel<T, true><<<dim3((unsigned)((p + 63) / 64), (unsigned)(ldk8 / 128)), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, other, Gt, ldk8, flag);
-    else encode_geno_kernel<T><<<dim3((unsigned)((p + 63) / 64), (unsigned)((ldk + 127) / 128)), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, other, Gt, ldk, flag);
-    params_geno_kernel<<<(unsigned)((p + 255) / 256), 256, 0, ctx->stream>>>(p, kmin, kmax, other, v0, dx, dlt);
-    PG_HIP(hipGetLastError());
+    int rcd = launch_detect<T>(ctx, n, p, X, ldX, kmin, kmax, other, Gt, ldk, ldk8, i8, v0, dx, dlt, flag);
+    if (rcd) return rcd;
     int hflag[2] = {0, 0};
     PG_HIP(hipMemcpyAsync(hflag, flag, 8, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(hipStreamSynchronize(ctx->stream));
     if (hflag[0] & 2) { *is_geno_host = 0; return PG_OK; }     // NaN / Inf: the fp32 kernel's propagation is the reference's
     if (hflag[0] & 1) {                                        // finite, not genotype-valued: X itself in two fp16 planes
         *is_geno_host = 2;
-        split_x_kernel<T><<<dim3((unsigned)((p + 63) / 64), (unsigned)((ldk + 127) / 128)), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, Gt, Gi, ldk);
+        split_x_kernel<T><<<tile_grid(ctx, (p + 63) / 64, (ldk + 127) / 128), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, Gt, Gi, ldk);
         params_split_kernel<<<(unsigned)((p + 255) / 256), 256, 0, ctx->stream>>>(p, kmin, kmax, v0, dx, dlt);
         PG_HIP(hipGetLastError());
         return launch_geno_gemm(ctx, n, p, Uprep, Gt, Gi, v0, dx, dlt, Xr, ldx, true);
     }
     *is_geno_host = 1;
     if (hflag[1]) {
-        if (i8) indicator_geno_kernel<T, true><<<dim3((unsigned)((p + 31) / 32), (unsigned)(ldk8 / 32)), 256, 0, ctx->stream>>>(n, p, X, ldX, other, Gi, ldk8);
-        else indicator_geno_kernel<T><<<dim3((unsigned)((p + 31) / 32), (unsigned)((ldk + 31) / 32)), 256, 0, ctx->stream>>>(n, p, X, ldX, other, Gi, ldk);
+        if (i8) indicator_geno_kernel<T, true><<<tile_grid(ctx, (p + 31) / 32, ldk8 / 32), 256, 0, ctx->stream>>>(n, p, X, ldX, other, Gi, ldk8);
+        else indicator_geno_kernel<T><<<tile_grid(ctx, (p + 31) / 32, (ldk + 31) / 32), 256, 0, ctx->stream>>>(n, p, X, ldX, other, Gi, ldk);
     }
     return launch_geno_gemm(ctx, n, p, Uprep, Gt, Gi, v0, dx, dlt, Xr, ldx, hflag[1] != 0, nullptr, i8);
 }
@@ -1151,21 +1365,17 @@ static int rotate_auto_any(pg_ctx *ctx, int64_t n, int64_t p, const float *U, in
     float *v0 = (float *)tail, *dx = v0 + p, *dlt = dx + p;
     int *kmin = (int *)(dlt + p), *kmax = kmin + p, *other = kmax + p;
     int *flag = other + p;
-    PG_HIP(hipMemsetAsync(flag, 0, 8, ctx->stream));
-    minmax_init_kernel<<<(unsigned)((p + 255) / 256), 256, 0, ctx->stream>>>(p, kmin, kmax, other);
-    minmax_geno_kernel<T><<<dim3((unsigned)((p + 63) / 64), (unsigned)((n + 255) / 256)), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, flag);
     const bool i8 = geno_i8_enabled();
     const long long ldk8 = prep_layout(n).ldk8;
-    if (i8) encode_geno_kernel<T, true><<<dim3((unsigned)((p + 63) / 64), (unsigned)(ldk8 / 128)), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, other, Gt, ldk8, flag);
-    else encode_geno_kernel<T><<<dim3((unsigned)((p + 63) / 64), (unsigned)((ldk + 127) / 128)), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, other, Gt, ldk, flag);
-    params_geno_kernel<<<(unsigned)((p + 255) / 256), 256, 0, ctx->stream>>>(p, kmin, kmax, other, v0, dx, dlt);
+    int rc = launch_detect<T>(ctx, n, p, X, ldX, kmin, kmax, other, Gt, ldk, ldk8, i8, v0, dx, dlt, flag);
+    if (rc) return rc;
     // genotype block with an imputed value: indicator plane; finite non-genotype block: X in two fp16 planes (overwrites Gt, Gi, params)
-    if (i8) indicator_geno_kernel<T, true><<<dim3((unsigned)((p + 31) / 32), (unsigned)(ldk8 / 32)), 256, 0, ctx->stream>>>(n, p, X, ldX, other, Gi, ldk8, flag);
-    else indicator_geno_kernel<T><<<dim3((unsigned)((p + 31) / 32), (unsigned)((ldk + 31) / 32)), 256, 0, ctx->stream>>>(n, p, X, ldX, other, Gi, ldk, flag);
-    split_x_kernel<T><<<dim3((unsigned)((p + 63) / 64), (unsigned)((ldk + 127) / 128)), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, Gt, Gi, ldk, flag);
+    if (i8) indicator_geno_kernel<T, true><<<tile_grid(ctx, (p + 31) / 32, ldk8 / 32), 256, 0, ctx->stream>>>(n, p, X, ldX, other, Gi, ldk8, flag);
+    else indicator_geno_kernel<T><<<tile_grid(ctx, (p + 31) / 32, (ldk + 31) / 32), 256, 0, ctx->stream>>>(n, p, X, ldX, other, Gi, ldk, flag);
+    split_x_kernel<T><<<tile_grid(ctx, (p + 63) / 64, (ldk + 127) / 128), 256, 0, ctx->stream>>>(n, p, X, ldX, kmin, kmax, Gt, Gi, ldk, flag);
     params_split_kernel<<<(unsigned)((p + 255) / 256), 256, 0, ctx->stream>>>(p, kmin, kmax, v0, dx, dlt, flag);
     PG_HIP(hipGetLastError());
-    int rc = launch_geno_gemm(ctx, n, p, Uprep, Gt, Gi, v0, dx, dlt, Xr, ldx, true, flag, i8);
+    rc = launch_geno_gemm(ctx, n, p, Uprep, Gt, Gi, v0, dx, dlt, Xr, ldx, true, flag, i8);
     if (rc) return rc;
     if constexpr (std::is_same<T, float>::value) {       // NaN / Inf block (float input only): the reference's propagation
         PG_REQUIRE(U && ldU >= n, "pg_rotate_auto_dev: U is needed for the fp32 fallback");
