@@ -434,6 +434,48 @@ int pg_kinship_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int 
                          double *acc);
 int pg_kinship_finish_dev(pg_ctx *ctx, int64_t n, int64_t p, const double *acc, float *K);
 
+/* ---- KING-robust relatedness, IBS similarity and per-sample QC counts on the int8 matrix pipe (csrc/king.hip), accumulated
+ * over the SNP batches of a stream.  Block conventions of pg_kinship_x_acc_dev / pg_kinship_bed_acc_dev; elements and hard calls as for
+ * LD above: missing is .bed code 01, NaN or +-Inf (an 8-bit block has no missing code), a SNP with a non-missing value other than
+ * exactly 0, 1, 2 counts as ALL missing for every sample.  Sample i at a SNP has m (called), h (called and 1), a (called and 0),
+ * b (called and 2); a pair (i, j) has the int32 sums over all SNPs of all batches
+ *     N = sum m_i m_j   HH = sum h_i h_j   IBS0 = sum (a_i b_j + b_i a_j)   Hij = sum h_i m_j   (Hij is not symmetric: Hji = Hij')
+ *     IBS1 = Hij + Hji - 2 HH,  IBS2 = N - IBS0 - IBS1,  all exact;
+ *     phi = float32((double)(HH - 2 IBS0) / (double)(Hij + Hji)), NaN when Hij + Hji == 0   (what plink2 --make-king prints)
+ *     ibs = float32(1 - (double)(IBS1 + 2 IBS0) / (double)(2 N)),  NaN when N == 0.
+ * A sample against itself or an exact copy gives phi = 0.5 exactly; phi does not depend on count_a1.
+ *   acc     : pg_king_acc_bytes(n, pb) device bytes on a 16-byte boundary for the largest batch pb used, opaque.  Its first
+ *             pg_king_zero_bytes(n) bytes (four n x n int32 accumulators, the totals of the batches without a missing call, the
+ *             per-sample counts) are zeroed by the caller before the first batch; the rest (flags and the int8 planes c = b - a, h, m
+ *             of one batch, n sample-major rows of pb rounded up to the K-tile of 128 SNPs) is rewritten by every batch.
+ *   pg_king_{bed,x}_acc_dev : add one batch of pb SNPs.  A batch without a missing call takes two int8 products per pair of 256-sample
+ *             tiles (c c', h h'; N and Hij grow by per-batch totals), any other five (c c', h h', m m', h m' and its transpose); the
+ *             same integers either way (PG_KING_PLANES=1 in the environment sends every batch the second way; tests and A/B timing).
+ *             "Without a missing call" is about the calls of hard-call SNPs: a SNP of an array that is not hard-call has all-zero
+ *             planes and does not count in the batch's N, on either path.  With PG_KING_TIMING=1 in the environment every batch
+ *             is bracketed by events and waited for, and pg_king_last_batch_ms gives the milliseconds of the calling thread's
+ *             last batch: encode (flags, screen, encode, totals) and pair kernel; same results (tools/bench_king.py).
+ *   pg_king_finish_dev : out (n x n float32, row-major, both triangles, bit-symmetric) = phi (what = 0) or ibs (what = 1).
+ *   pg_king_counts_dev : counts5 = five n x n int32 matrices one after the other, every entry of both triangles: N, HH, IBS0,
+ *             Hij (row i, column j: i's het calls where j is called) and IBS1; sample5 = n x 5 int64, row i = n_obs, n_miss, n0, n1, n2
+ *             of sample i (count_a1 swaps n0 and n2; a SNP that is not hard-call adds 1 to every n_miss).
+ *   pg_sample_stats_{bed,x}_acc_dev : the count kernel alone: ADDS the batch's n x 5 counts (the layout above) to sample5, which the
+ *             caller zeroes before the first batch.  Scratch comes from the context.
+ * Batches are summed in call order on the context's stream; every count is an integer, so the result does not depend on the batch
+ * boundaries.  The total number of SNPs over all batches must stay below 2^31 (every count fits int32).
+ * PG_EINVAL for NULL pointers, an accumulator off 16 bytes, n < 1, n >= 2^20, pb < 1, pb >= 2^31, `what` other than 0 or 1 or strides
+ * too small; PG_ENOTSUP for an unknown dtype: a refused call enqueues nothing.  pg_king_acc_bytes and pg_king_zero_bytes are 0 for a
+ * refused shape. */
+size_t pg_king_acc_bytes(int64_t n, int64_t pb);
+size_t pg_king_zero_bytes(int64_t n);
+int pg_king_last_batch_ms(float *encode_ms, float *pair_ms);
+int pg_king_bed_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, void *acc);
+int pg_king_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, void *acc);
+int pg_king_finish_dev(pg_ctx *ctx, int64_t n, const void *acc, int what, float *out);
+int pg_king_counts_dev(pg_ctx *ctx, int64_t n, const void *acc, int32_t *counts5, int64_t *sample5);
+int pg_sample_stats_bed_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, int64_t *sample5);
+int pg_sample_stats_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, int64_t *sample5);
+
 /* ---- lmm/lmm.py:124-125: K <- Z K Z' for the optional design matrix Z (n x q) of the random effect, K (q x q).  Z and K may each be
  * float32 or float64 (z_is_f64 / k_is_f64), row-major with row strides ldz / ldk, on the device; out = float32 (n x n, row stride ldo),
  * what lmm.py:127-128 hands to the eigensolver.  Two fp64-MFMA products and one rounding. */

@@ -70,6 +70,35 @@ class PackedBed:
         snps = None if self.snps is None else [self.snps[j] for j in idx]
         return PackedBed(np.ascontiguousarray(self.data[idx]), self.n, count_A1=self.count_A1, snps=snps)
 
+    def take_samples(self, index):
+        """A new PackedBed over the selected samples: `index` is a boolean mask of length n (what lmm.unrelated returns) or integer
+        indices in any order (negative ones count from the end).  The records are repacked on the host, a few thousand SNPs at a time;
+        count_A1 stays, `snps` is copied.  A mask of another length, an index outside the samples or a selection without any sample
+        raises ValueError (no consumer takes n = 0)."""
+        idx = np.asarray(index)
+        if idx.dtype == np.bool_:
+            if idx.shape != (self.n,):
+                raise ValueError(f"a mask over {self.n} samples has shape ({self.n},), not {idx.shape}")
+            idx = np.flatnonzero(idx)
+        else:
+            if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+                raise ValueError("index must be a boolean mask of length n or a 1-D array of integer sample indices")
+            idx = idx.astype(np.int64)
+            if idx.size and (idx.min() < -self.n or idx.max() >= self.n):
+                raise ValueError(f"sample index out of range for {self.n} samples")
+            idx = np.where(idx < 0, idx + self.n, idx)
+        m = int(idx.size)
+        if m < 1:
+            raise ValueError("the selection holds no sample")
+        byte, shift = idx >> 2, ((idx & 3) * 2).astype(np.uint8)
+        out = np.zeros((self.p, (m + 3) // 4), np.uint8)
+        step = max(1, (64 << 20) // m)              # 64 MiB of unpacked codes at a time
+        for s in range(0, self.p, step):
+            codes = (np.asarray(self.data[s:s + step])[:, byte] >> shift[None, :]) & 3
+            c = np.concatenate([codes, np.zeros((codes.shape[0], (-m) % 4), np.uint8)], axis=1).reshape(codes.shape[0], -1, 4)
+            out[s:s + step] = c[:, :, 0] | (c[:, :, 1] << 2) | (c[:, :, 2] << 4) | (c[:, :, 3] << 6)
+        return PackedBed(out, m, count_A1=self.count_A1, snps=None if self.snps is None else list(self.snps))
+
     def to_float(self, impute=True):
         """Host decode to the (n, p) float32 matrix the reference's callers build (NaN or column-mean for missing calls)."""
         shifts = np.arange(4, dtype=np.uint8) * 2

@@ -41,7 +41,8 @@ from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_re
 from . import model as _model
 
 __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
-           "kinship", "ld", "ld_window", "ld_prune", "clump", "prs", "prs_weights"] + _model.__all__
+           "kinship", "ld", "ld_window", "ld_prune", "clump", "prs", "prs_weights", "king", "ibs", "sample_stats", "related_pairs",
+           "unrelated"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -1096,6 +1097,181 @@ def clump(df, X, p1=1e-4, p2=1e-2, r2=0.5, window=250, col="p_wald", chrom=None,
     res = pd.DataFrame(out, columns=list(out))
     res["members"] = pd.Series([cand[mem] for _, mem in clumps], dtype=object, index=res.index)
     return res
+
+
+# ---- KING-robust relatedness and sample QC (csrc/king.hip) -------------------------------------------------------------------
+# SNPs per batch by default: the read-modify-write of the int32 accumulators (up to 20 n^2 bytes per batch on and below the diagonal) is
+# about 650 / pb of the batch's products (5 n^2 pb int8 operations) at 5 TB/s and 2.5 POP/s: 4 % at 16 384
+_KING_BATCH = 16384
+_SAMPLE_COLS = ("n_obs", "n_miss", "n0", "n1", "n2", "miss", "het")
+
+
+def _king_source(X, who, snp_batch):
+    _check_snp_batch(snp_batch)
+    X = _ld_source(X, who)
+    if X.shape[1] >= 2 ** 31:
+        raise ValueError(f"{who} counts in int32: p = {X.shape[1]} SNPs is 2^31 or more")
+    return X
+
+
+def _sample_frame(cnt, samples=None):
+    """The per-sample frame of an (n, 5) int64 array n_obs, n_miss, n0, n1, n2."""
+    out = {col: cnt[:, k] for k, col in enumerate(_SAMPLE_COLS[:5])}
+    tot = cnt[:, 0] + cnt[:, 1]
+    out["miss"] = cnt[:, 1] / tot.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["het"] = np.where(cnt[:, 0] > 0, cnt[:, 3] / cnt[:, 0].astype(np.float64), np.nan)
+    df = pd.DataFrame(out, columns=list(_SAMPLE_COLS))
+    if samples is not None:
+        df["samples"] = samples
+    return df
+
+
+def _king_stream(X, what, counts, device, snp_batch, verbose, stats, who):
+    """The streamed pair counts: SNP batches from the feed (_feed._Feed) through pg_king_{bed,x}_acc_dev into the int32 accumulators, then
+    pg_king_finish_dev (what: 0 phi, 1 ibs) and, with `counts`, pg_king_counts_dev.  Returns the matrix, or (matrix, dict)."""
+    L, t0 = _lib.load(), time.time()
+    src = _describe(X)
+    n, p = src.n, src.p
+    if not L.pg_king_acc_bytes(n, 1):
+        raise ValueError(f"{who} takes fewer than 2^20 samples, not n={n}")
+    _gpus()
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
+        # everything that lives beside the accumulators until the context closes: the float32 result and, with `counts`, the five int32
+        # matrices and the n x 5 counts that pg_king_counts_dev writes after the stream; _fit_batch must see them to size the batch honestly
+        out_bytes = 4 * n * n + ((20 * n * n + 40 * n) if counts else 0)
+        pb = _fit_batch(ctx, snp_batch, _KING_BATCH, p, 128, lambda pb: int(L.pg_king_acc_bytes(n, pb)) + out_bytes + 2 * pb * src.row_bytes,
+                        f"{who}: n={n}", "int32 accumulators 16 n^2, the result 4 n^2 (24 n^2 with counts), int8 planes 3 n per SNP, two batch slots")
+        dacc = ctx.alloc(L.pg_king_acc_bytes(n, pb))
+        dout = ctx.alloc(4 * n * n)
+        batches = feed.batches(pb)
+        _lib.check(L.pg_memset(ctx.handle, dacc.ptr, 0, L.pg_king_zero_bytes(n)), "pg_memset")
+        for s, e, slot in batches:
+            _call_dev(L, "pg_king_{}_acc_dev", src, (ctx.handle, n, e - s), slot, e - s, (dacc.ptr,))
+            _log(verbose - 1, f"{who}: SNPs [{s},{e}) queued")
+        _lib.check(L.pg_king_finish_dev(ctx.handle, n, dacc.ptr, what, dout.ptr), "pg_king_finish_dev")
+        if counts:
+            dc, ds = ctx.alloc(20 * n * n), ctx.alloc(40 * n)
+            _lib.check(L.pg_king_counts_dev(ctx.handle, n, dacc.ptr, dc.ptr, ds.ptr), "pg_king_counts_dev")
+        ctx.sync()
+        out = dout.download((n, n), np.float32)
+        if counts:
+            mats = dc.download((5, n, n), np.int32)
+            extra = {"N": mats[0], "HH": mats[1], "IBS0": mats[2], "Hij": mats[3], "samples": _sample_frame(ds.download((n, 5), np.int64))}
+    _stream_stats(stats, src, pb, t0)
+    _log(verbose, f"{who}: {p} SNPs with {n} individuals in {time.time() - t0:.3f} s")
+    return (out, extra) if counts else out
+
+
+def king(X, *, counts=False, device=0, snp_batch=None, verbose=0, stats=None):
+    """The KING-robust kinship matrix of the samples (Manichaikul et al. 2010; the estimator of plink2 --make-king): the (n, n) float32
+    matrix phi, both triangles, bit-symmetric.  It needs no allele frequencies, so one stream over the genotypes is enough: duplicates and
+    twins, sample swaps and close relatives show before the first scan.
+
+    X (n, p): whatever snp_stats takes — a PackedBed, or an int8, uint8, float32 or float64 array in C or Fortran order, pinned or
+    pageable — streamed in SNP batches of `snp_batch` columns through the two-slot feed, encoded into int8 planes on the device and
+    multiplied on the int8 matrix pipe (csrc/king.hip).  Hard calls only, as for `ld`: missing is .bed code 01, NaN or +-Inf; a SNP with
+    an observed value other than 0, 1, 2 counts as all missing for every sample.  Over the SNPs where both samples of a pair are called,
+      N = jointly called SNPs, HH = both het, IBS0 = opposite homozygotes, Hij = i's het calls where j is called (Hji its transpose)
+      phi = (HH - 2 IBS0) / (Hij + Hji): one fp64 division of exact int32 counts, one rounding to float32; NaN when Hij + Hji == 0.
+    A sample against itself or an exact duplicate gives exactly 0.5; unrelated pairs scatter around 0 (negative values mean population
+    structure); phi does not depend on count_A1, nor, bit for bit, on the batch boundaries.  `counts=True` returns (phi, dict) with the
+    (n, n) int32 matrices N, HH, IBS0, Hij (Hij in full, not symmetric) and `samples`, the frame of sample_stats from the same stream.
+    `stats` receives batches, bytes_in, seconds.  Accumulators that do not fit the device raise PgError.  Refused with ValueError before
+    any device work: X not 2-D or of another dtype, an empty X, n >= 2^20, p >= 2^31, a bad snp_batch."""
+    return _king_stream(_king_source(X, "king", snp_batch), 0, bool(counts), device, snp_batch, verbose, stats, "king")
+
+
+def ibs(X, *, counts=False, device=0, snp_batch=None, verbose=0, stats=None):
+    """The identity-by-state similarity of the samples from the stream of `king` (same arguments, same counts): the (n, n) float32 matrix
+    1 - (IBS1 + 2 IBS0) / (2 N), the share of alleles two samples have in common over the SNPs where both are called (PLINK's --distance
+    ibs), IBS1 = Hij + Hji - 2 HH; NaN when N == 0.  A sample against itself gives exactly 1."""
+    return _king_stream(_king_source(X, "ibs", snp_batch), 1, bool(counts), device, snp_batch, verbose, stats, "ibs")
+
+
+def sample_stats(X, samples=None, device=0, snp_batch=None, verbose=0, stats=None):
+    """Per-sample quality control from the raw genotypes, read once where they lie (PLINK's --missing and --het on samples): a DataFrame
+    of n rows with n_obs, n_miss, n0, n1, n2 (int64: called and missing calls, calls that are 0, 1, 2; count_A1 swaps n0 and n2),
+    miss = n_miss / p and het = n1 / n_obs (NaN at n_obs == 0), and `samples` when given.  X as for `king`, with its hard-call rule: a
+    SNP that is not hard-call adds 1 to every n_miss.  This is the count kernel of `king` alone, bandwidth-bound, without pair products.
+    `stats` receives batches, bytes_in, seconds.  Refused with ValueError before any device work: X not 2-D or of another dtype, an empty
+    X, `samples` of another length, a bad snp_batch."""
+    X = _king_source(X, "sample_stats", snp_batch)
+    L, t0 = _lib.load(), time.time()
+    src = _describe(X)
+    n, p = src.n, src.p
+    if samples is not None and len(samples) != n:
+        raise ValueError(f"shape mismatch: {len(samples)} sample names for {n} samples")
+    if not L.pg_king_acc_bytes(n, 1):
+        raise ValueError(f"sample_stats takes fewer than 2^20 samples, not n={n}")
+    _gpus()
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
+        pb = _fit_batch(ctx, snp_batch, _lm_batch(src), p, 128, lambda pb: 40 * n + 4 * pb + 2 * pb * src.row_bytes,
+                        f"sample_stats: n={n}, p={p}", "40 n bytes of counts, two batch slots")
+        ds = ctx.alloc(40 * n)
+        batches = feed.batches(pb)
+        _lib.check(L.pg_memset(ctx.handle, ds.ptr, 0, 40 * n), "pg_memset")
+        for s, e, slot in batches:
+            _call_dev(L, "pg_sample_stats_{}_acc_dev", src, (ctx.handle, n, e - s), slot, e - s, (ds.ptr,))
+            _log(verbose - 1, f"sample_stats: SNPs [{s},{e}) queued")
+        ctx.sync()
+        cnt = ds.download((n, 5), np.int64)
+    _stream_stats(stats, src, pb, t0)
+    _log(verbose, f"Sample statistics: {p} SNPs with {n} individuals in {time.time() - t0:.3f} s")
+    return _sample_frame(cnt, samples)
+
+
+def _check_phi(phi, cutoff):
+    phi = np.asarray(phi)
+    if phi.ndim != 2 or phi.shape[0] != phi.shape[1]:
+        raise ValueError(f"phi must be a square (n, n) matrix, not of shape {phi.shape}")
+    if isinstance(cutoff, bool) or not isinstance(cutoff, (int, float, np.integer, np.floating)) or not -np.inf < cutoff <= 0.5:
+        raise ValueError(f"cutoff must be a number of at most 0.5 (a duplicate's kinship), not {cutoff!r}")
+    return phi
+
+
+def related_pairs(phi, cutoff=0.0884):
+    """The related pairs of a kinship matrix of `king`: a DataFrame i, j, phi of the pairs i < j with phi[i, j] > cutoff, sorted by
+    descending phi, then i, then j; pure NumPy.  NaN is never related.  The usual cut-offs are the geometric midpoints between the
+    expected kinships of the degrees: 0.354 duplicates and monozygotic twins, 0.177 first degree, 0.0884 second degree (the default),
+    0.0442 third degree.  Refused with ValueError: a phi that is not square, a cutoff above 0.5 or not a number."""
+    phi = _check_phi(phi, cutoff)
+    with np.errstate(invalid="ignore"):
+        i, j = np.nonzero(np.triu(phi > cutoff, 1))
+    v = phi[i, j]
+    order = np.lexsort((j, i, -v.astype(np.float64)))
+    return pd.DataFrame({"i": i[order].astype(np.int64), "j": j[order].astype(np.int64), "phi": v[order]}, columns=["i", "j", "phi"])
+
+
+def unrelated(phi, cutoff=0.0884):
+    """A boolean keep-mask over the samples of a kinship matrix of `king` in which no two kept samples are related (phi > cutoff, the
+    cut-offs of related_pairs): hand it to PackedBed.take_samples or index the rows of X with it.  The rule is greedy and deterministic
+    on the graph of related pairs: while an edge remains, drop the vertex of largest current degree, ties going to the largest index.
+    That is NOT the algorithm of plink2 --king-cutoff, which may keep another (equally unrelated) subset; pure NumPy and Python on the
+    thresholded pairs.  Refusals as for related_pairs."""
+    import heapq
+    phi = _check_phi(phi, cutoff)
+    n = phi.shape[0]
+    pairs = related_pairs(phi, cutoff)
+    adj = [set() for _ in range(n)]
+    for i, j in zip(pairs["i"].tolist(), pairs["j"].tolist()):
+        adj[i].add(j)
+        adj[j].add(i)
+    keep = np.ones(n, bool)
+    heap = [(-len(adj[v]), -v) for v in range(n) if adj[v]]      # entries go stale when a neighbour leaves: checked when popped
+    heapq.heapify(heap)
+    while heap:
+        d, v = heapq.heappop(heap)
+        d, v = -d, -v
+        if not keep[v] or d != len(adj[v]) or d == 0:
+            continue
+        keep[v] = False
+        for u in adj[v]:
+            adj[u].discard(v)
+            if adj[u]:
+                heapq.heappush(heap, (-len(adj[u]), -u))
+        adj[v] = set()
+    return keep
 
 
 # ---- polygenic scores (csrc/prs.hip, DESIGN §4.12) -----------------------------------------------------------------------------------------
