@@ -359,7 +359,9 @@ int pg_rotate_dev(pg_ctx *ctx, int64_t n, int64_t p, const float *U, int64_t ldU
  * tests/test_gpu_rotate.py; 1/7 of its time).  PG_GENO_I8=0 selects the r2-r3 kernel instead: U split into two fp16 planes by
  * round-to-nearest (residual <= 2^-23 |U|), fp32 accumulation on the fp16 MFMA pipe.  A column may also hold ONE other
  * value anywhere (missing calls imputed with the column mean, experiments/benchmarks/benchmarks.py:243-244): such blocks
- * take a second, accumulating pass on the 0/1 indicator plane.
+ * take a second, accumulating pass of the SAME kernel on the 0/1 indicator plane — int8 like the codes, exact like them:
+ * Xr = float32(fma(delta_g 2^(E_k - 22), U'ind, Xr)) for every row of the block (the fp16 kernel's with PG_GENO_I8=0).  The whole
+ * genotype path is integer sums, one fp64 fma and one rounding per pass: tests/test_gpu_rotate_i8_exact.py predicts every bit.
  * Finite blocks that are not genotype-valued (imputed dosages, any float X) take the same GEMM with X itself split into two
  * fp16 planes (per-column power-of-two scale, residual <= 2^-23 |x|): two passes, still 3x faster than pg_rotate_dev.
  *   pg_geno_prep_dev   : once per U -> Uprep (pg_geno_prep_bytes(n) bytes, device)

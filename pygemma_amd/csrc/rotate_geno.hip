@@ -791,8 +791,9 @@ __global__ __launch_bounds__(512, 1) void kin_geno_kernel(GenoParams gp) { geno_
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The same rotation on the int8 matrix pipe (r4): genotype CODES only (path (1) above and .bed blocks; indicator and split-plane
-// passes stay on fp16).  v_mfma_i32_16x16x64_i8 takes the cycles of v_mfma_f32_16x16x32_f16 for twice the K
+// The same rotation on the int8 matrix pipe (r4): genotype blocks (paths (1) and (2) above and .bed blocks): the codes and, where a
+// column holds an imputed value or a missing call, the 0/1 indicator plane in a second, accumulating pass of this kernel
+// (launch_geno_gemm, i8codes).  Only split-plane blocks (3) stay on fp16.  v_mfma_i32_16x16x64_i8 takes the cycles of v_mfma_f32_16x16x32_f16 for twice the K
 // (profiles/r03_mfma_sustained.txt: 2 620 TOP/s sustained against 1 285 TF), the codes 0/1/2 are exact in int8 and the integer
 // accumulation is EXACT, so all of the error sits in the representation of U:
 //     U[i][k] = 2^(E_k - 22) * (q_ik + e),  q_ik = rint(U[i][k] * 2^(22 - E_k)) = 65536 d2 + 256 d1 + d0,  d in [-128, 127],  |e| <= 1/2
