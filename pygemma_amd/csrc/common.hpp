@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -69,4 +70,13 @@ struct pg_ctx {
 namespace pg {
 int ensure(pg_ctx *ctx, void **ptr, size_t *have, size_t need);
 int build_npsum_plan(pg_ctx *ctx, int64_t n);
+
+// the parts of a work area start on 256 bytes
+static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// an environment switch (PG_LD_PLANES, PG_KING_PLANES, PG_KINSHIP_FP32, ...) is on: set and not 0.  Read per call: the tests switch inside one process
+static inline bool env_flag(const char *name)
+{
+    const char *e = getenv(name);
+    return e && atoi(e) != 0;
+}
 }  // namespace pg

@@ -21,9 +21,8 @@
 // are screened for SNPs that are not hard-call in a pass of their own BEFORE the encode (their calls are then classed missing), so no plane
 // is ever written and taken back.
 //
-// The pair kernel is the 256 x 256 int8 GEMM tile of ld_pair_kernel (v_mfma_i32_16x16x64_i8, 128-byte LDS rows, the same swizzle,
-// global_load_lds staging, two buffers, accumulators released to LDS for the epilogue) with samples as output rows and the batch's SNPs as
-// K.  The grid is (lower-triangle pairs of sample tiles) x (products); a workgroup adds its product into its accumulator.
+// The pair kernel runs the 256 x 256 int8 GEMM tile of i8_pair.hpp with samples as output rows and the batch's SNPs as K.  The grid is
+// (lower-triangle pairs of sample tiles) x (products); a workgroup adds its product into its accumulator.
 //   no missing call in the batch (device flag): m = 1 on every hard-call SNP, so N grows by the batch's hard-call SNP count and Hij by i's
 //     het total of the batch (king_fold_kernel adds them to a scalar and a vector that the finish adds back): products c c' and h h' only;
 //   general: c c', h h', m m', h m' (rows I, columns J) and h m' with the tiles swapped (rows J, columns I: the other triangle of Hij,
@@ -34,24 +33,18 @@
 // SNPs only (pb minus the screen's flags) and the het totals never see such a SNP.
 // PG_KING_TIMING=1 puts events around the encode and the pair kernel of every batch and waits for them (pg_king_last_batch_ms reads the
 // two times; tools/bench_king.py).  The results are the same; the call no longer returns before the batch is done.
-#include "common.hpp"
+#include "geno_src.hpp"
+#include "i8_pair.hpp"
 
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 namespace pg {
 
-typedef int intx4 __attribute__((ext_vector_type(4)));
-
-constexpr int KG_BK = 128;          // SNPs per K-tile: 128-byte LDS rows
+constexpr int KG_BK = I8P_BK;       // SNPs per K-tile
 constexpr int KG_T = 256;           // samples per output tile side
 constexpr int KG_ES = 256;          // samples per encode workgroup
 constexpr int KG_EK = 4;            // K-tiles per encode workgroup: fewer atomics per sample
 constexpr int KG_EROW = 144;        // LDS bytes per sample row of the encode tile: 128 class bytes and one 16-byte pad
-constexpr int KG_TBUF = 256 * 128;
-constexpr int KG_LDW = 260;         // words per staged accumulator row (see rotate_geno_i8_kernel)
-constexpr int KG_LDS = 128 * KG_LDW * 4 > 4 * KG_TBUF ? 128 * KG_LDW * 4 : 4 * KG_TBUF;
 constexpr long long KG_MAXN = 1LL << 20;       // exclusive: every grid dimension fits (the finish: n / 32 tiles a side)
 constexpr long long KG_MAXPB = 1LL << 31;      // exclusive: every count fits int32
 
@@ -62,20 +55,19 @@ struct KingLayout {
     long long ldk;
     size_t mat, hfast, samp, nfast, zero, flag, hb, bad, planes, plane, total;
 };
-static size_t kg_up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static KingLayout king_layout(long long n, long long pb)
 {
     KingLayout L;
     L.ldk = (pb + KG_BK - 1) / KG_BK * KG_BK;
-    L.mat = kg_up256((size_t)n * n * 4);
+    L.mat = up256((size_t)n * n * 4);
     L.hfast = 4 * L.mat;
-    L.samp = L.hfast + kg_up256((size_t)n * 8);
-    L.nfast = L.samp + kg_up256((size_t)n * 40);
+    L.samp = L.hfast + up256((size_t)n * 8);
+    L.nfast = L.samp + up256((size_t)n * 40);
     L.zero = L.nfast + 256;
     L.flag = L.zero;
     L.hb = L.flag + 256;
-    L.bad = L.hb + kg_up256((size_t)n * 4);
-    L.planes = L.bad + kg_up256((size_t)pb * 4);
+    L.bad = L.hb + up256((size_t)n * 4);
+    L.planes = L.bad + up256((size_t)pb * 4);
     L.plane = (size_t)n * L.ldk;
     L.total = L.planes + 3 * L.plane;
     return L;
@@ -123,7 +115,7 @@ struct KingEnc {
     unsigned long long *samp;         // n x 5: n_obs, n_miss, n0, n1, n2
 };
 
-// LAYOUT 0: .bed records (T = unsigned char), 1: SNP-major array, 2: sample-major array.  Workgroup (x: KG_EK K-tiles, y: 256 samples).
+// Workgroup (x: KG_EK K-tiles, y: 256 samples).
 template <class T, int LAYOUT, bool IMG> __global__ __launch_bounds__(256) void king_encode_kernel(KingEnc q, const T *X)
 {
     __shared__ __attribute__((aligned(16))) unsigned char cls[KG_ES * KG_EROW];
@@ -136,7 +128,7 @@ template <class T, int LAYOUT, bool IMG> __global__ __launch_bounds__(256) void 
     int miss = 0;
     for (long long kt = kt0; kt < kt1; kt++) {
         const long long g0 = kt * KG_BK;
-        if constexpr (LAYOUT == 0) {
+        if constexpr (LAYOUT == GENO_BED) {
             const long long nbytes = ((long long)q.n + 3) / 4;
             for (int e = tid; e < KG_BK * (KG_ES / 4); e += 256) {
                 const int sl = e >> 6, b = e & 63;
@@ -152,7 +144,7 @@ template <class T, int LAYOUT, bool IMG> __global__ __launch_bounds__(256) void 
                     cls[(4 * b + k) * KG_EROW + sl] = (unsigned char)cl;
                 }
             }
-        } else if constexpr (LAYOUT == 1) {
+        } else if constexpr (LAYOUT == GENO_SNP) {
             const long long i = i0 + tid;
             for (int sl = 0; sl < KG_BK; sl++) {
                 const long long g = g0 + sl;
@@ -219,10 +211,10 @@ template <class T, int LAYOUT, bool IMG> static int launch_king_encode(pg_ctx *c
 {
     const T *Xt = static_cast<const T *>(X);
     const unsigned sy = (unsigned)((q.n + KG_ES - 1) / KG_ES);
-    if constexpr (LAYOUT == 1) {
+    if constexpr (LAYOUT == GENO_SNP) {
         king_screen_snp_kernel<T><<<(unsigned)q.pb, 256, 0, ctx->stream>>>(q.n, q.ld, Xt, bad);
         PG_HIP(hipGetLastError());
-    } else if constexpr (LAYOUT == 2) {
+    } else if constexpr (LAYOUT == GENO_SAMPLE) {
         king_screen_sample_kernel<T><<<dim3((unsigned)((q.pb + 63) / 64), (unsigned)((q.n + 1023) / 1024)), 256, 0, ctx->stream>>>(q.n, q.pb, q.ld, Xt, bad);
         PG_HIP(hipGetLastError());
     }
@@ -235,21 +227,11 @@ template <class T, int LAYOUT, bool IMG> static int launch_king_encode(pg_ctx *c
 
 template <bool IMG> static int king_encode_any(pg_ctx *ctx, const KingEnc &q, const void *X, int dtype, int snp_major, int *bad)
 {
-    if (dtype < 0) return launch_king_encode<unsigned char, 0, IMG>(ctx, q, X, bad);
-    if (snp_major) {
-        switch (dtype) {
-            case PG_DTYPE_INT8: return launch_king_encode<signed char, 1, IMG>(ctx, q, X, bad);
-            case PG_DTYPE_UINT8: return launch_king_encode<unsigned char, 1, IMG>(ctx, q, X, bad);
-            case PG_DTYPE_FLOAT32: return launch_king_encode<float, 1, IMG>(ctx, q, X, bad);
-            default: return launch_king_encode<double, 1, IMG>(ctx, q, X, bad);
-        }
-    }
-    switch (dtype) {
-        case PG_DTYPE_INT8: return launch_king_encode<signed char, 2, IMG>(ctx, q, X, bad);
-        case PG_DTYPE_UINT8: return launch_king_encode<unsigned char, 2, IMG>(ctx, q, X, bad);
-        case PG_DTYPE_FLOAT32: return launch_king_encode<float, 2, IMG>(ctx, q, X, bad);
-        default: return launch_king_encode<double, 2, IMG>(ctx, q, X, bad);
-    }
+    if (dtype < 0) return launch_king_encode<unsigned char, GENO_BED, IMG>(ctx, q, X, bad);
+    return geno_dispatch(dtype, snp_major != 0, [&](auto src) {
+        using S = decltype(src);
+        return launch_king_encode<typename S::type, S::layout, IMG>(ctx, q, X, bad);
+    });
 }
 
 // a batch without a missing call: its N and Hij are totals, kept apart from the matrices
@@ -272,8 +254,6 @@ __global__ __launch_bounds__(256) void king_fold_kernel(int n, long long pb, int
 }
 
 // ---- the pair kernel --------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int king_swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
 struct KingPair {
     int n, KT, planes;
     long long ldk;
@@ -285,7 +265,6 @@ struct KingPair {
 
 __global__ __launch_bounds__(512, 1) void king_pair_kernel(KingPair q)
 {
-    extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     const int prod = blockIdx.y;      // 0: c c', 1: h h', 2: m m', 3: h_I m_J', 4: h_J m_I'
     if (prod >= 2 && !(q.planes || *q.flag)) return;
     long long I = (long long)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
@@ -297,90 +276,32 @@ __global__ __launch_bounds__(512, 1) void king_pair_kernel(KingPair q)
     const long long abase = (prod == 4 ? J : I) * KG_T, bbase = (prod == 4 ? I : J) * KG_T;
     int *const dst = q.acc[prod < 3 ? prod : 3];
 
-    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int wm = wave >> 1, wn = wave & 1;          // 4 x 2 waves, each 64 (A rows) x 128 (B rows)
-    const int lrow = lane >> 3, lchunk = lane & 7, chunk0 = lane >> 4;
-    int *const stg = reinterpret_cast<int *>(lds);
+    const int tid = threadIdx.x;
+    const I8pLane ln = i8p_lane();
+    const int *const stg = i8p_staged();
     intx4 acc[4][8];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-#pragma unroll
-            for (int e = 0; e < 4; e++) acc[i][j][e] = 0;
-    // DMA sources: this lane's row of the four 8-row strips of the wave's 32 rows, either operand.  Rows past sample n repeat the last
-    // sample: their products are never read.
+    i8p_zero(acc);
+    // DMA sources.  Rows past sample n repeat the last sample: their products are never read.
     const signed char *srcA[4], *srcB[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) {
-        const int row = wave * 32 + 8 * t + lrow;
+        const int row = i8p_src_row(ln, t);
         const long long ga = min(abase + row, (long long)q.n - 1), gb = min(bbase + row, (long long)q.n - 1);
-        srcA[t] = q.img + pa * q.plane + (size_t)ga * q.ldk + king_swz(row, lchunk) * 16;
-        srcB[t] = q.img + pb * q.plane + (size_t)gb * q.ldk + king_swz(row, lchunk) * 16;
+        srcA[t] = q.img + pa * q.plane + (size_t)ga * q.ldk + i8p_src_byte(ln, row);
+        srcB[t] = q.img + pb * q.plane + (size_t)gb * q.ldk + i8p_src_byte(ln, row);
     }
-    auto dma = [&](int stage) {
-        unsigned char *dA = lds + (stage & 1) * 2 * KG_TBUF + (wave * 32) * 128, *dB = dA + KG_TBUF;
-        const size_t k = (size_t)stage * KG_BK;
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(srcA[t] + k),
-                                             (__attribute__((address_space(3))) void *)(dA + 8 * t * 128), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(srcB[t] + k),
-                                             (__attribute__((address_space(3))) void *)(dB + 8 * t * 128), 16, 0, 0);
-        }
-    };
-    dma(0);
-    for (int kt = 0; kt < q.KT; kt++) {
-        if (kt + 1 < q.KT) { dma(kt + 1); asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                                  // K-tile kt of every wave has landed
-        const unsigned char *Acur = lds + (kt & 1) * 2 * KG_TBUF, *Bcur = Acur + KG_TBUF;
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-            intx4 fa[4], fb[8];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int row = wm * 64 + i * 16 + (lane & 15);
-                fa[i] = *reinterpret_cast<const intx4 *>(Acur + row * 128 + king_swz(row, 4 * ks + chunk0) * 16);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const int row = wn * 128 + j * 16 + (lane & 15);
-                fb[j] = *reinterpret_cast<const intx4 *>(Bcur + row * 128 + king_swz(row, 4 * ks + chunk0) * 16);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();                                  // every wave has read buffer kt & 1: stage kt + 2 may overwrite it
-    }
+    i8p_products(ln, srcA, srcB, q.KT, acc);
     // ---- epilogue: the accumulators meet through LDS, one 128-row half of A at a time, and are added to the matrix
 #pragma unroll 1
     for (int half = 0; half < 2; half++) {
-        if ((wm >> 1) == half) {
-            const int rb = (wm & 1) * 64;
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 8; j++)
-#pragma unroll
-                    for (int e = 0; e < 4; e++) stg[(rb + i * 16 + 4 * (lane >> 4) + e) * KG_LDW + wn * 128 + j * 16 + (lane & 15)] = acc[i][j][e];
-        }
-        __syncthreads();
+        i8p_stage(ln, half, acc);
         for (int idx = tid; idx < 128 * KG_T; idx += 512) {
             const int sa = idx >> 8, sb = idx & (KG_T - 1);
             const long long i = abase + half * 128 + sa, j = bbase + sb;
-            if (i < q.n && j < q.n) dst[i * q.n + j] += stg[sa * KG_LDW + sb];
+            if (i < q.n && j < q.n) dst[i * q.n + j] += stg[sa * I8P_LDW + sb];
         }
         __syncthreads();
     }
-}
-
-static bool king_env(const char *name)
-{
-    const char *e = getenv(name);
-    return e && atoi(e) != 0;
 }
 
 // ---- finish -------------------------------------------------------------------------------------------------------------------------------
@@ -473,7 +394,7 @@ static int king_batch(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dty
     char *base = static_cast<char *>(acc);
     const long long nt = (n + KG_T - 1) / KG_T;
     PG_HIP(hipSetDevice(ctx->device));
-    const bool timing = king_env("PG_KING_TIMING");
+    const bool timing = env_flag("PG_KING_TIMING");
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (timing) {
         for (int k = 0; k < 3; k++) PG_HIP(hipEventCreate(&ev[k]));
@@ -487,7 +408,7 @@ static int king_batch(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dty
     e.flag = flag; e.hb = hb; e.samp = reinterpret_cast<unsigned long long *>(base + L.samp);
     const int rc = king_encode_any<true>(ctx, e, X, dtype, snp_major, bad);
     if (rc != PG_OK) return rc;
-    const int planes = king_env("PG_KING_PLANES");      // read per call, like PG_LD_PLANES: the tests switch it inside one process
+    const int planes = env_flag("PG_KING_PLANES");
     king_fold_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>((int)n, pb, planes, flag, dtype < 0 ? nullptr : bad, hb,
                                                                               reinterpret_cast<long long *>(base + L.hfast),
                                                                               reinterpret_cast<long long *>(base + L.nfast));
@@ -496,13 +417,8 @@ static int king_batch(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dty
     KingPair q;
     q.n = (int)n; q.KT = (int)(L.ldk / KG_BK); q.planes = planes; q.ldk = L.ldk; q.img = e.img; q.plane = L.plane; q.flag = flag;
     for (int k = 0; k < 4; k++) q.acc[k] = reinterpret_cast<int *>(base + k * L.mat);
-    static std::atomic<unsigned long long> lds_set{0};      // the kernel's LDS limit, once per device
-    const unsigned long long bit = 1ULL << (ctx->device & 63);
-    if (!(lds_set.load(std::memory_order_acquire) & bit)) {
-        PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&king_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, KG_LDS));
-        lds_set.fetch_or(bit, std::memory_order_release);
-    }
-    king_pair_kernel<<<dim3((unsigned)(nt * (nt + 1) / 2), 5), 512, KG_LDS, ctx->stream>>>(q);
+    PG_HIP(i8p_lds_limit<king_pair_kernel>(ctx->device));
+    king_pair_kernel<<<dim3((unsigned)(nt * (nt + 1) / 2), 5), 512, I8P_LDS, ctx->stream>>>(q);
     PG_HIP(hipGetLastError());
     if (timing) {
         PG_HIP(hipEventRecord(ev[2], ctx->stream));
@@ -518,7 +434,7 @@ static int king_batch(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dty
 static int king_stats(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ld, int snp_major, int count_a1, int64_t *sample5)
 {
     PG_HIP(hipSetDevice(ctx->device));
-    const size_t need = 256 + kg_up256((size_t)pb * 4);
+    const size_t need = 256 + up256((size_t)pb * 4);
     const int rc = ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, need);
     if (rc != PG_OK) return rc;
     char *base = static_cast<char *>(ctx->scratch);
@@ -560,7 +476,7 @@ extern "C" size_t pg_king_zero_bytes(int64_t n)
     PG_REQUIRE(ctx && X && dst, who ": NULL argument");                                                                                     \
     PG_REQUIRE(king_shape_ok(n, pb) && ldX >= (snp_major ? n : pb), who ": bad shape n=%lld pb=%lld ldX=%lld snp_major=%d", (long long)n,  \
                (long long)pb, (long long)ldX, snp_major);                                                                                   \
-    if (dtype < PG_DTYPE_INT8 || dtype > PG_DTYPE_FLOAT64) {                                                                                \
+    if (!dtype_known(dtype)) {                                                                                                              \
         set_error(who ": unknown dtype %d", dtype);                                                                                         \
         return PG_ENOTSUP;                                                                                                                  \
     }

@@ -18,18 +18,15 @@
 // of one batch's fp32 sum; pg_kinship_finish_dev divides by p, rounds to float32 and mirrors.
 // Float blocks (not exact in fp16) and every block under PG_KINSHIP_FP32=1 take the fp32 path instead: Zt = (x - s) / sd, SNP-major
 // float32, and the fp32-MFMA syrk of rotate.hip with an accumulating epilogue into the same accumulator.
-#include "common.hpp"
+#include "geno_src.hpp"
 
 #include <cmath>
-#include <cstdlib>
 
 namespace pg {
 
 int kin_geno_gemm(pg_ctx *ctx, long long n, int kts, const unsigned short *A, long long ldA, const unsigned short *B, long long ldB,
                   const float *scale, const double *vk, const int *kflag, double *acc);            // rotate_geno.hip
 int syrk_acc_fp32(pg_ctx *ctx, long long kdim, long long n, const float *Zt, long long ldz, double *acc);   // rotate.hip
-
-enum { LAY_BED = 0, LAY_SAMPLE = 1, LAY_SNP = 2 };   // packed .bed records | (n x pb) sample-major | (pb x n) SNP-major
 
 struct KinPar {
     double *mu, *sh, *w, *isd, *r;   // per SNP of the batch: imputation value, shift, weight of R, 1/sd of the fp32 path, integer centre
@@ -41,7 +38,6 @@ struct KinLayout {
     long long kts, ldA, ldB, ldz;
     size_t a, b, vpart, v, par, flag, total;
 };
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static KinLayout kin_layout(long long n, long long pb)
 {
     KinLayout L{};
@@ -170,7 +166,7 @@ template <class T, int LAY>
 __device__ __forceinline__ void kin_load_tile(double (*tv)[65], long long n, long long pb, const T *X, long long ldX, int count_a1,
                                               long long j0, long long i0)
 {
-    if constexpr (LAY == LAY_BED) {
+    if constexpr (LAY == GENO_BED) {
         for (int e = threadIdx.x; e < 64 * 16; e += blockDim.x) {
             const int sl = e >> 4, b = e & 15;
             const long long j = j0 + sl, byte = i0 / 4 + b;
@@ -183,9 +179,9 @@ __device__ __forceinline__ void kin_load_tile(double (*tv)[65], long long n, lon
         }
     } else {
         for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) {
-            const int sl = (LAY == LAY_SAMPLE) ? (e & 63) : (e >> 6), rl = (LAY == LAY_SAMPLE) ? (e >> 6) : (e & 63);   // contiguous side fastest
+            const int sl = (LAY == GENO_SAMPLE) ? (e & 63) : (e >> 6), rl = (LAY == GENO_SAMPLE) ? (e >> 6) : (e & 63);   // contiguous side fastest
             const long long j = j0 + sl, i = i0 + rl;
-            tv[sl][rl] = (j < pb && i < n) ? (double)((LAY == LAY_SAMPLE) ? X[i * ldX + j] : X[j * ldX + i]) : 0.0;
+            tv[sl][rl] = (j < pb && i < n) ? (double)((LAY == GENO_SAMPLE) ? X[i * ldX + j] : X[j * ldX + i]) : 0.0;
         }
     }
 }
@@ -321,12 +317,8 @@ __global__ __launch_bounds__(256) void kin_finish_kernel(long long n, long long 
     }
 }
 
-// PG_KINSHIP_FP32=1 sends every block to the fp32 path (A/B, tests); read per call
-static bool kin_fp32_forced()
-{
-    const char *e = getenv("PG_KINSHIP_FP32");
-    return e && atoi(e) != 0;
-}
+// PG_KINSHIP_FP32=1 sends every block to the fp32 path (A/B, tests)
+static bool kin_fp32_forced() { return env_flag("PG_KINSHIP_FP32"); }
 
 static KinPar kin_par(char *base, const KinLayout &L, long long pb)
 {
@@ -358,16 +350,15 @@ static int kin_batch(pg_ctx *ctx, long long n, long long pb, const T *X, long lo
     return syrk_acc_fp32(ctx, pb, n, Zt, L.ldz, acc);
 }
 
-template <class T>
-static int kin_x(pg_ctx *ctx, long long n, long long pb, const T *X, long long ldX, bool snp_major, int standardize, bool fp16, const KinLayout &L,
-                 char *base)
+template <class T, int LAY>
+static int kin_x(pg_ctx *ctx, long long n, long long pb, const T *X, long long ldX, int standardize, bool fp16, const KinLayout &L, char *base)
 {
+    constexpr bool snp_major = LAY == GENO_SNP;
     const KinPar P = kin_par(base, L, pb);
     PG_HIP(hipMemsetAsync(P.flag, 0, 16, ctx->stream));
-    if (snp_major) kin_x_stats_kernel<T, true><<<dim3((unsigned)pb), 256, 0, ctx->stream>>>(n, pb, X, ldX, standardize, P);
-    else kin_x_stats_kernel<T, false><<<dim3((unsigned)((pb + 63) / 64)), 256, 0, ctx->stream>>>(n, pb, X, ldX, standardize, P);
+    kin_x_stats_kernel<T, snp_major><<<dim3((unsigned)(snp_major ? pb : (pb + 63) / 64)), 256, 0, ctx->stream>>>(n, pb, X, ldX, standardize, P);
     PG_HIP(hipGetLastError());
-    return snp_major ? kin_batch<T, LAY_SNP>(ctx, n, pb, X, ldX, 0, fp16, L, base, P) : kin_batch<T, LAY_SAMPLE>(ctx, n, pb, X, ldX, 0, fp16, L, base, P);
+    return kin_batch<T, LAY>(ctx, n, pb, X, ldX, 0, fp16, L, base, P);
 }
 
 }  // namespace pg
@@ -393,7 +384,7 @@ extern "C" int pg_kinship_bed_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const 
     PG_HIP(hipMemsetAsync(P.flag, 0, 16, ctx->stream));
     kin_bed_stats_kernel<<<dim3((unsigned)pb), 256, 0, ctx->stream>>>(n, pb, bed, ldb, count_a1, standardize, P);
     PG_HIP(hipGetLastError());
-    return kin_batch<unsigned char, LAY_BED>(ctx, n, pb, bed, ldb, count_a1, !kin_fp32_forced(), L, base, P);
+    return kin_batch<unsigned char, GENO_BED>(ctx, n, pb, bed, ldb, count_a1, !kin_fp32_forced(), L, base, P);
 }
 
 extern "C" int pg_kinship_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, int standardize,
@@ -402,17 +393,14 @@ extern "C" int pg_kinship_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const vo
     PG_REQUIRE(ctx && X && acc, "pg_kinship_x_acc_dev: NULL argument");
     PG_REQUIRE(n > 0 && pb > 0 && ldX >= (snp_major ? n : pb) && pb < (1LL << 31) && n < (1LL << 31),
                "pg_kinship_x_acc_dev: bad shape n=%lld pb=%lld ldX=%lld snp_major=%d", (long long)n, (long long)pb, (long long)ldX, snp_major);
-    PG_REQUIRE(dtype >= PG_DTYPE_INT8 && dtype <= PG_DTYPE_FLOAT64, "pg_kinship_x_acc_dev: unknown dtype %d", dtype);
+    PG_REQUIRE(dtype_known(dtype), "pg_kinship_x_acc_dev: unknown dtype %d", dtype);
     PG_HIP(hipSetDevice(ctx->device));
     const KinLayout L = kin_layout(n, pb);
-    const bool sm = snp_major != 0, fp16 = !kin_fp32_forced();
-    char *base = (char *)acc;
-    switch (dtype) {
-        case PG_DTYPE_INT8: return kin_x(ctx, n, pb, (const signed char *)X, ldX, sm, standardize, fp16, L, base);
-        case PG_DTYPE_UINT8: return kin_x(ctx, n, pb, (const unsigned char *)X, ldX, sm, standardize, fp16, L, base);
-        case PG_DTYPE_FLOAT32: return kin_x(ctx, n, pb, (const float *)X, ldX, sm, standardize, false, L, base);
-        default: return kin_x(ctx, n, pb, (const double *)X, ldX, sm, standardize, false, L, base);
-    }
+    const bool fp16 = !kin_fp32_forced();      // kin_batch takes the fp16 pipe for 8-bit values only
+    return geno_dispatch(dtype, snp_major != 0, [&](auto src) {
+        using S = decltype(src);
+        return kin_x<typename S::type, S::layout>(ctx, n, pb, (const typename S::type *)X, ldX, standardize, fp16, L, (char *)acc);
+    });
 }
 
 extern "C" int pg_kinship_finish_dev(pg_ctx *ctx, int64_t n, int64_t p, const double *acc, float *K)

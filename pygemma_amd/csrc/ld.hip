@@ -13,10 +13,7 @@
 // the K-tile of 128 samples, ZERO in every plane past sample n (a pad sample with m = 1 would count in N), then one int4 per SNP:
 // {sum x, sum x^2, missing calls, not hard-call}.  A SNP that is not hard-call has all-zero planes and n missing calls.
 //
-// The pair kernel is the 256 x 256 int8 GEMM tile of rotate_geno_i8_kernel (v_mfma_i32_16x16x64_i8, 128-byte LDS rows, the same swizzle,
-// global_load_lds staging, accumulators released to LDS for the epilogue) in a plain two-buffer loop: all eight waves stage their 32 rows of
-// both operands of K-tile t + 1, wait for their own loads of K-tile t, meet at a barrier and issue the 64 MFMAs of their 64 x 128 quarter.
-// A workgroup owns a pair of SNP tiles of LD_T1 = 252 SNPs.  When no SNP of either tile holds a missing call — imputed data, 8-bit arrays —
+// The pair kernel runs the 256 x 256 int8 GEMM tile of i8_pair.hpp.  A workgroup owns a pair of SNP tiles of LD_T1 = 252 SNPs.  When no SNP of either tile holds a missing call — imputed data, 8-bit arrays —
 // it takes ONE product: rows = the x planes of 252 SNPs a side, N = n, and Sa, Sb, Saa, Sbb are the per-SNP totals.  Otherwise it walks the
 // 3 x 3 pairs of sub-tiles of LD_T3 = 84 SNPs with "planes as output rows": each 128-row half of an operand tile holds 42 SNPs as rows
 // [0, 42) x, [42, 84) m, [84, 126) x^2 (two rows spare), so that a staged half carries whole SNPs, and the epilogue picks the six sums out of
@@ -24,26 +21,20 @@
 // PG_LD_PLANES=1 sends every tile pair down the three-plane path (tests, A/B timing).
 // Two output mappings: a dense block r[ia][ib], and a band, band[j][k] = r(j, j + 1 + k), for which only the tile pairs (and, inside the
 // three-plane path, the sub-tile pairs) that meet the band are launched or run.
-#include "common.hpp"
+#include "geno_src.hpp"
+#include "i8_pair.hpp"
 
-#include <atomic>
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 namespace pg {
 
-typedef int intx4 __attribute__((ext_vector_type(4)));
-
-constexpr int LD_BK = 128;        // samples per K-tile: 128-byte LDS rows
+constexpr int LD_BK = I8P_BK;     // samples per K-tile
 constexpr int LD_T1 = 252;        // SNPs per tile side, one-product path
 constexpr int LD_T3 = 84;         // SNPs per sub-tile side, three-plane path: 2 halves x 42 SNPs x 3 planes
 constexpr int LD_H3 = 42;
 constexpr long long LD_MAXN = 1LL << 28;      // exclusive: every sum fits int32 (4 n < 2^31), every product int64
 constexpr long long LD_MAXPE = 1LL << 31;
-constexpr int LD_TBUF = 256 * 128;
-constexpr int LD_LDW = 260;       // words per staged accumulator row (see rotate_geno_i8_kernel)
-constexpr int LD_LDS = 128 * LD_LDW * 4 > 4 * LD_TBUF ? 128 * LD_LDW * 4 : 4 * LD_TBUF;
 
 struct LdLayout {
     long long ldk;
@@ -82,7 +73,7 @@ struct LdEnc {
     int4 *tot;
 };
 
-// LAYOUT 0: .bed records (T = unsigned char), 1: SNP-major array, 2: sample-major array.  A lane encodes 16 consecutive samples of one SNP:
+// A lane encodes 16 consecutive samples of one SNP:
 // three 16-byte stores.  SNP-major sources: one workgroup per SNP, lanes along the samples.  Sample-major: lane = SNP (the loads of a wavefront
 // are adjacent), workgroup = 64 SNPs x 1024 samples.  The totals are integer atomics: the same bits in any order.
 template <class T, int LAYOUT> __global__ __launch_bounds__(256) void ld_encode_kernel(LdEnc q, const T *X)
@@ -91,7 +82,7 @@ template <class T, int LAYOUT> __global__ __launch_bounds__(256) void ld_encode_
     const int ngrp = (int)(q.ldk / 16);
     long long g;
     int grp0, grp1, step;
-    if constexpr (LAYOUT == 2) {
+    if constexpr (LAYOUT == GENO_SAMPLE) {
         const long long chunk = blockIdx.x / q.ngb, gb = blockIdx.x % q.ngb;
         g = gb * 64 + lane;
         grp0 = (int)chunk * 64 + wave; grp1 = min(ngrp, (int)chunk * 64 + 64); step = 4;
@@ -110,12 +101,12 @@ template <class T, int LAYOUT> __global__ __launch_bounds__(256) void ld_encode_
                 const int i = grp * 16 + s;
                 int code = 0, m = 0, bd = 0;
                 if (i < q.n) {
-                    if constexpr (LAYOUT == 0) {
+                    if constexpr (LAYOUT == GENO_BED) {
                         const int c = (X[(size_t)g * q.ld + (i >> 2)] >> (2 * (i & 3))) & 3;      // 00 -> 0, 10 -> 1, 11 -> 2, 01 missing
                         m = c != 1;
                         code = c == 0 ? 0 : (c == 2 ? 1 : (c == 3 ? 2 : 0));
                         if (q.count_a1 && m) code = 2 - code;
-                    } else if constexpr (LAYOUT == 1) ld_classify<T>(X[(size_t)g * q.ld + i], code, m, bd);
+                    } else if constexpr (LAYOUT == GENO_SNP) ld_classify<T>(X[(size_t)g * q.ld + i], code, m, bd);
                     else ld_classify<T>(X[(size_t)i * q.ld + g], code, m, bd);
                     nm += 1 - m;
                 }
@@ -128,7 +119,7 @@ template <class T, int LAYOUT> __global__ __launch_bounds__(256) void ld_encode_
             *reinterpret_cast<uint4 *>(row + 2 * plane + (size_t)grp * 16) = make_uint4(qw[0], qw[1], qw[2], qw[3]);
         }
     }
-    if constexpr (LAYOUT != 2) {      // the wavefront is one SNP's
+    if constexpr (LAYOUT != GENO_SAMPLE) {      // the wavefront is one SNP's
         for (int k = 1; k < 64; k <<= 1) {
             s1 += __shfl_xor(s1, k, 64); s2 += __shfl_xor(s2, k, 64); nm += __shfl_xor(nm, k, 64); bad += __shfl_xor(bad, k, 64);
         }
@@ -161,7 +152,7 @@ __global__ __launch_bounds__(256) void ld_fixup_kernel(LdEnc q)
 template <class T, int LAYOUT> static int launch_ld_encode(pg_ctx *ctx, LdEnc q, const void *X, const char *who)
 {
     long long grid = q.pb;
-    if (LAYOUT == 2) {
+    if (LAYOUT == GENO_SAMPLE) {
         q.ngb = (q.pb + 63) / 64;
         grid = q.ngb * ((q.ldk / 16 + 63) / 64);
     }
@@ -169,7 +160,7 @@ template <class T, int LAYOUT> static int launch_ld_encode(pg_ctx *ctx, LdEnc q,
     PG_HIP(hipMemsetAsync(q.tot + q.at, 0, (size_t)q.pb * 16, ctx->stream));
     ld_encode_kernel<T, LAYOUT><<<(unsigned)grid, 256, 0, ctx->stream>>>(q, static_cast<const T *>(X));
     PG_HIP(hipGetLastError());
-    if (LAYOUT != 0) {
+    if (LAYOUT != GENO_BED) {
         ld_fixup_kernel<<<(unsigned)q.pb, 256, 0, ctx->stream>>>(q);
         PG_HIP(hipGetLastError());
     }
@@ -177,8 +168,6 @@ template <class T, int LAYOUT> static int launch_ld_encode(pg_ctx *ctx, LdEnc q,
 }
 
 // ---- the pair kernel --------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ld_swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
 struct LdPair {
     int n, KT, band, planes, tiles_b;
     long long ldk;
@@ -214,9 +203,8 @@ __device__ __forceinline__ void ld_store(const LdPair &q, long long o, bool vali
 
 __global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
 {
-    extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
-    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int wm = wave >> 1, wn = wave & 1;          // 4 x 2 waves, each 64 (A rows) x 128 (B rows)
+    const int tid = threadIdx.x;
+    const I8pLane ln = i8p_lane();
     const long long tile_a = blockIdx.x / q.tiles_b, tile_b = blockIdx.x % q.tiles_b + (q.band ? tile_a : 0);
     const long long abase = q.a0 + tile_a * LD_T1, bbase = q.b0 + tile_b * LD_T1;
     const long long aend = q.a0 + q.na, bend = q.b0 + q.nb;      // one past the last SNP with data on either side
@@ -229,8 +217,7 @@ __global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
     }
     const bool three = __syncthreads_or(miss) != 0;
     const int T = three ? LD_T3 : LD_T1, nsub = three ? 3 : 1;
-    const int lrow = lane >> 3, lchunk = lane & 7, chunk0 = lane >> 4;
-    int *const stg = reinterpret_cast<int *>(lds);
+    const int *const stg = i8p_staged();
 
 #pragma unroll 1
     for (int sub = 0; sub < nsub * nsub; sub++) {
@@ -242,80 +229,29 @@ __global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
         if (bs0 >= bs1 || (q.band && bs0 + T <= as0 + 1)) continue;
         const bool data = bs0 < bend;                                                        // band: partners at or past `have` are NaN
         intx4 acc[4][8];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-#pragma unroll
-                for (int e = 0; e < 4; e++) acc[i][j][e] = 0;
+        i8p_zero(acc);
         if (data) {
-            // DMA sources: this lane's row of the four 8-row strips of the wave's 32 rows, either operand.  Rows without a SNP (the spare rows,
-            // SNPs past the window) repeat the window's last SNP: their products are never read.
+            // DMA sources.  Rows without a SNP (the spare rows, SNPs past the window) repeat the window's last SNP: their products are never read.
             const signed char *srcA[4], *srcB[4];
 #pragma unroll
             for (int t = 0; t < 4; t++) {
-                const int row = wave * 32 + 8 * t + lrow;
+                const int row = i8p_src_row(ln, t);
                 int pl = 0, s = row;
                 if (three) {
                     const int h = row >> 7, rr = row & 127;
                     pl = min(rr / LD_H3, 2); s = h * LD_H3 + rr % LD_H3;
                 }
                 const long long ga = min(as0 + s, aend - 1), gb = min(bs0 + s, bend - 1);
-                srcA[t] = q.A + ((size_t)pl * q.pea + ga) * q.ldk + ld_swz(row, lchunk) * 16;
-                srcB[t] = q.B + ((size_t)pl * q.peb + gb) * q.ldk + ld_swz(row, lchunk) * 16;
+                srcA[t] = q.A + ((size_t)pl * q.pea + ga) * q.ldk + i8p_src_byte(ln, row);
+                srcB[t] = q.B + ((size_t)pl * q.peb + gb) * q.ldk + i8p_src_byte(ln, row);
             }
-            auto dma = [&](int stage) {
-                unsigned char *dA = lds + (stage & 1) * 2 * LD_TBUF + (wave * 32) * 128, *dB = dA + LD_TBUF;
-                const size_t k = (size_t)stage * LD_BK;
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(srcA[t] + k),
-                                                     (__attribute__((address_space(3))) void *)(dA + 8 * t * 128), 16, 0, 0);
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(srcB[t] + k),
-                                                     (__attribute__((address_space(3))) void *)(dB + 8 * t * 128), 16, 0, 0);
-                }
-            };
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stores of the previous epilogue are not counted against the loads below
-            dma(0);
-            for (int kt = 0; kt < q.KT; kt++) {
-                if (kt + 1 < q.KT) { dma(kt + 1); asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();                                  // K-tile kt of every wave has landed
-                const unsigned char *Acur = lds + (kt & 1) * 2 * LD_TBUF, *Bcur = Acur + LD_TBUF;
-#pragma unroll
-                for (int ks = 0; ks < 2; ks++) {
-                    intx4 fa[4], fb[8];
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        const int row = wm * 64 + i * 16 + (lane & 15);
-                        fa[i] = *reinterpret_cast<const intx4 *>(Acur + row * 128 + ld_swz(row, 4 * ks + chunk0) * 16);
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; j++) {
-                        const int row = wn * 128 + j * 16 + (lane & 15);
-                        fb[j] = *reinterpret_cast<const intx4 *>(Bcur + row * 128 + ld_swz(row, 4 * ks + chunk0) * 16);
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; j++)
-#pragma unroll
-                        for (int i = 0; i < 4; i++) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[i], fb[j], acc[i][j], 0, 0, 0);
-                }
-                __syncthreads();                                  // every wave has read buffer kt & 1: stage kt + 2 may overwrite it
-            }
+            i8p_products(ln, srcA, srcB, q.KT, acc);
         }
         // ---- epilogue: the accumulators meet through LDS, one 128-row half of A at a time
 #pragma unroll 1
         for (int half = 0; half < 2; half++) {
-            if ((wm >> 1) == half) {
-                const int rb = (wm & 1) * 64;
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 8; j++)
-#pragma unroll
-                        for (int e = 0; e < 4; e++) stg[(rb + i * 16 + 4 * (lane >> 4) + e) * LD_LDW + wn * 128 + j * 16 + (lane & 15)] = acc[i][j][e];
-            }
-            __syncthreads();
+            i8p_stage(ln, half, acc);
             const int ha = three ? LD_H3 : 128;                   // A SNPs in this half
             for (int idx = tid; idx < ha * T; idx += 512) {
                 const int sa = idx / T, sb = idx - sa * T;
@@ -330,13 +266,13 @@ __global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
                 const bool valid = jb < bend;
                 long long N = 0, Sa = 0, Sb = 0, Saa = 0, Sbb = 0, Sab = 0;
                 if (valid && three) {
-                    const int *s = stg + sa * LD_LDW + (sb / LD_H3) * 128 + sb % LD_H3;      // [plane of a][plane of b] at (pa 42) rows, (pb 42) columns
-                    Sab = s[0];                        Sb = s[LD_H3 * LD_LDW];                 Sa = s[LD_H3];
-                    N = s[LD_H3 * LD_LDW + LD_H3];     Saa = s[2 * LD_H3 * LD_LDW + LD_H3];    Sbb = s[LD_H3 * LD_LDW + 2 * LD_H3];
+                    const int *s = stg + sa * I8P_LDW + (sb / LD_H3) * 128 + sb % LD_H3;      // [plane of a][plane of b] at (pa 42) rows, (pb 42) columns
+                    Sab = s[0];                        Sb = s[LD_H3 * I8P_LDW];                 Sa = s[LD_H3];
+                    N = s[LD_H3 * I8P_LDW + LD_H3];     Saa = s[2 * LD_H3 * I8P_LDW + LD_H3];    Sbb = s[LD_H3 * I8P_LDW + 2 * LD_H3];
                 } else if (valid) {
                     const int4 a = q.ta[ja], b = q.tb[jb];
                     N = q.n; Sa = a.x; Saa = a.y; Sb = b.x; Sbb = b.y;
-                    Sab = stg[sa * LD_LDW + sb];
+                    Sab = stg[sa * I8P_LDW + sb];
                 }
                 ld_store(q, o, valid, N, Sa, Sb, Saa, Sbb, Sab);
             }
@@ -345,24 +281,13 @@ __global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
     }
 }
 
-static bool ld_force_planes()
-{
-    const char *e = getenv("PG_LD_PLANES");
-    return e && atoi(e) != 0;
-}
-
 static int launch_ld_pair(pg_ctx *ctx, LdPair q, long long tiles_a, long long tiles_b, const char *who)
 {
     PG_REQUIRE(tiles_a * tiles_b < (1LL << 31), "%s: too many tiles (%lld x %lld)", who, tiles_a, tiles_b);
     q.tiles_b = (int)tiles_b;
-    q.planes = ld_force_planes();      // read per call, like PG_GENO_I8: the tests switch it inside one process
-    static std::atomic<unsigned long long> lds_set{0};      // the kernel's LDS limit, once per device
-    const unsigned long long bit = 1ULL << (ctx->device & 63);
-    if (!(lds_set.load(std::memory_order_acquire) & bit)) {
-        PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ld_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LD_LDS));
-        lds_set.fetch_or(bit, std::memory_order_release);
-    }
-    ld_pair_kernel<<<(unsigned)(tiles_a * tiles_b), 512, LD_LDS, ctx->stream>>>(q);
+    q.planes = env_flag("PG_LD_PLANES");
+    PG_HIP(i8p_lds_limit<ld_pair_kernel>(ctx->device));
+    ld_pair_kernel<<<(unsigned)(tiles_a * tiles_b), 512, I8P_LDS, ctx->stream>>>(q);
     PG_HIP(hipGetLastError());
     return PG_OK;
 }
@@ -400,7 +325,7 @@ extern "C" int pg_ld_encode_bed_dev(pg_ctx *ctx, int64_t n, int64_t pb, const un
                (long long)at);
     if (pb == 0) return PG_OK;
     PG_HIP(hipSetDevice(ctx->device));
-    return launch_ld_encode<unsigned char, 0>(ctx, ld_enc(n, pb, ldb, count_a1, image, pe, at), bed, "pg_ld_encode_bed_dev");
+    return launch_ld_encode<unsigned char, GENO_BED>(ctx, ld_enc(n, pb, ldb, count_a1, image, pe, at), bed, "pg_ld_encode_bed_dev");
 }
 
 extern "C" int pg_ld_encode_x_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, void *image, int64_t pe,
@@ -411,28 +336,17 @@ extern "C" int pg_ld_encode_x_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void
     PG_REQUIRE(ld_shape_ok(n, pe) && pb >= 0 && at >= 0 && at + pb <= pe && ldX >= (snp_major ? n : pb),
                "pg_ld_encode_x_dev: bad shape n=%lld pb=%lld ldX=%lld snp_major=%d pe=%lld at=%lld", (long long)n, (long long)pb, (long long)ldX, snp_major,
                (long long)pe, (long long)at);
-    if (dtype < PG_DTYPE_INT8 || dtype > PG_DTYPE_FLOAT64) {
+    if (!dtype_known(dtype)) {
         set_error("pg_ld_encode_x_dev: unknown dtype %d", dtype);
         return PG_ENOTSUP;
     }
     if (pb == 0) return PG_OK;
     PG_HIP(hipSetDevice(ctx->device));
     const LdEnc q = ld_enc(n, pb, ldX, 0, image, pe, at);
-    const char *who = "pg_ld_encode_x_dev";
-    if (snp_major) {
-        switch (dtype) {
-            case PG_DTYPE_INT8: return launch_ld_encode<signed char, 1>(ctx, q, X, who);
-            case PG_DTYPE_UINT8: return launch_ld_encode<unsigned char, 1>(ctx, q, X, who);
-            case PG_DTYPE_FLOAT32: return launch_ld_encode<float, 1>(ctx, q, X, who);
-            default: return launch_ld_encode<double, 1>(ctx, q, X, who);
-        }
-    }
-    switch (dtype) {
-        case PG_DTYPE_INT8: return launch_ld_encode<signed char, 2>(ctx, q, X, who);
-        case PG_DTYPE_UINT8: return launch_ld_encode<unsigned char, 2>(ctx, q, X, who);
-        case PG_DTYPE_FLOAT32: return launch_ld_encode<float, 2>(ctx, q, X, who);
-        default: return launch_ld_encode<double, 2>(ctx, q, X, who);
-    }
+    return geno_dispatch(dtype, snp_major != 0, [&](auto src) {
+        using S = decltype(src);
+        return launch_ld_encode<typename S::type, S::layout>(ctx, q, X, "pg_ld_encode_x_dev");
+    });
 }
 
 // Rows move towards the front in runs of `from` SNPs, in stream order: source and destination of one copy never overlap.  That is

@@ -19,13 +19,12 @@
 // Determinism: an output element is one fixed chain — chunk after chunk, step after step, the four k-groups inside the
 // instruction — whatever the SNP's slot, tile, batch or row pitch; samples >= n enter as exact zeros and pad bytes are never
 // read.  No split over samples, no atomics: a row depends only on its SNP and on (W, Y).
-#include "common.hpp"
+#include "geno_src.hpp"
 
 #include <cmath>
 
 namespace pg {
 
-enum { LM_BED = 0, LM_SAMPLE = 1, LM_SNP = 2 };   // packed .bed records | (n x pb) sample-major | (pb x n) SNP-major
 
 constexpr int LM_KC = 64;                          // samples per chunk: 4 k-groups of 16
 constexpr int LM_RT = 2;                           // 16-SNP row tiles per wavefront
@@ -177,7 +176,7 @@ struct LmArgs {
 
 // a lane's run of 16 samples of one SNP as it is stored
 template <class T, int LAY> struct LmRaw { T v[16]; };
-template <class T> struct LmRaw<T, LM_BED> { unsigned w; };   // 16 two-bit calls
+template <class T> struct LmRaw<T, GENO_BED> { unsigned w; };   // 16 two-bit calls
 
 // samples [i, i + 16) of SNP g (i a multiple of 16); samples >= n become the value 0 and their bytes are not read.  vec (uniform): the
 // block's base and row pitch allow 16-byte (.bed: 4-byte) loads
@@ -185,7 +184,7 @@ template <class T, int LAY>
 __device__ __forceinline__ void lm_load(LmRaw<T, LAY> &r, const LmArgs &a, long long g, long long i, bool vec)
 {
     const T *X = static_cast<const T *>(a.X);
-    if constexpr (LAY == LM_BED) {
+    if constexpr (LAY == GENO_BED) {
         const long long bpr = ((long long)a.n + 3) / 4, b0 = i >> 2;
         const unsigned char *rec = X + g * a.ldX;
         unsigned w = 0;
@@ -202,7 +201,7 @@ __device__ __forceinline__ void lm_load(LmRaw<T, LAY> &r, const LmArgs &a, long 
                 if (i + s >= a.n) w = (w & ~(3u << (2 * s))) | (fill << (2 * s));
         }
         r.w = w;
-    } else if constexpr (LAY == LM_SNP) {
+    } else if constexpr (LAY == GENO_SNP) {
         const T *row = X + g * a.ldX + i;
         if (vec && i + 16 <= a.n) __builtin_memcpy(r.v, __builtin_assume_aligned(row, 16), 16 * sizeof(T));
         else {
@@ -219,7 +218,7 @@ __device__ __forceinline__ void lm_load(LmRaw<T, LAY> &r, const LmArgs &a, long 
 template <class T, int LAY>
 __device__ __forceinline__ double lm_val(const LmRaw<T, LAY> &r, int s, double mu, int count_a1)
 {
-    if constexpr (LAY == LM_BED) {
+    if constexpr (LAY == GENO_BED) {
         const unsigned code = (r.w >> (2 * s)) & 3u;
         return code == 1u ? mu : (code == 2u ? 1.0 : (((code == 3u) != (count_a1 != 0)) ? 2.0 : 0.0));
     } else {
@@ -248,7 +247,7 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lm_kernel(LmArgs a, bool vec)
     bool called[LM_RT];
 #pragma unroll
     for (int rt = 0; rt < LM_RT; rt++) { mu[rt] = 0.0; called[rt] = true; }
-    if constexpr (LAY == LM_BED) {
+    if constexpr (LAY == GENO_BED) {
         // pre-pass over the record: exact counts of het / hom-2 / missing calls (kin_bed_stats_kernel's convention); a missing call
         // takes the fp64 mean of the called genotypes rounded to float32
 #pragma unroll
@@ -370,12 +369,12 @@ static int launch_lm(pg_ctx *ctx, int nt, const LmArgs &a, bool vec)
     return PG_OK;
 }
 
-template <class T>
-static int launch_lm_x(pg_ctx *ctx, int nt, bool snp_major, const LmArgs &a)
+template <class T, int LAY>
+static int launch_lm_x(pg_ctx *ctx, int nt, const LmArgs &a)
 {
     // 16-byte loads of a SNP-major row need the base and the row pitch on 16 bytes; the values read are the same either way
-    const bool vec = snp_major && ((uintptr_t)a.X % 16 == 0) && ((size_t)a.ldX * sizeof(T)) % 16 == 0;
-    return snp_major ? launch_lm<T, LM_SNP>(ctx, nt, a, vec) : launch_lm<T, LM_SAMPLE>(ctx, nt, a, false);
+    const bool vec = LAY == GENO_SNP && ((uintptr_t)a.X % 16 == 0) && ((size_t)a.ldX * sizeof(T)) % 16 == 0;
+    return launch_lm<T, LAY>(ctx, nt, a, vec);
 }
 
 // the argument checks the three entry points share (after their NULL checks); what: the entry's name
@@ -467,18 +466,15 @@ extern "C" int pg_lm_x_dev(pg_ctx *ctx, int64_t n, int c, int t, int64_t pb, con
     if (rc) return rc;
     PG_REQUIRE(pb >= 0 && pb < (1LL << 31) && ldX >= (snp_major ? n : pb) && ldo >= pb, "pg_lm_x_dev: bad shape pb=%lld ldX=%lld ldo=%lld snp_major=%d",
                (long long)pb, (long long)ldX, (long long)ldo, snp_major);
-    PG_REQUIRE(dtype >= PG_DTYPE_INT8 && dtype <= PG_DTYPE_FLOAT64, "pg_lm_x_dev: unknown dtype %d", dtype);
+    PG_REQUIRE(dtype_known(dtype), "pg_lm_x_dev: unknown dtype %d", dtype);
     if (pb == 0) return PG_OK;
     PG_HIP(hipSetDevice(ctx->device));
     const LmArgs a = lm_args(n, c, t, pb, X, ldX, 0, work, beta, se, tau, F, ldo);
     const int nt = lm_np(c, t) / 16;
-    const bool sm = snp_major != 0;
-    switch (dtype) {
-        case PG_DTYPE_INT8: rc = launch_lm_x<signed char>(ctx, nt, sm, a); break;
-        case PG_DTYPE_UINT8: rc = launch_lm_x<unsigned char>(ctx, nt, sm, a); break;
-        case PG_DTYPE_FLOAT32: rc = launch_lm_x<float>(ctx, nt, sm, a); break;
-        default: rc = launch_lm_x<double>(ctx, nt, sm, a); break;
-    }
+    rc = geno_dispatch(dtype, snp_major != 0, [&](auto src) {
+        using S = decltype(src);
+        return launch_lm_x<typename S::type, S::layout>(ctx, nt, a);
+    });
     if (rc) return rc;
     return pval ? lm_pvalues(ctx, n, c, t, pb, F, pval, ldo) : PG_OK;
 }
@@ -495,7 +491,7 @@ extern "C" int pg_lm_bed_dev(pg_ctx *ctx, int64_t n, int c, int t, int64_t pb, c
     PG_HIP(hipSetDevice(ctx->device));
     const LmArgs a = lm_args(n, c, t, pb, bed, ldb, count_a1 != 0, work, beta, se, tau, F, ldo);
     const bool vec = ((uintptr_t)bed % 4 == 0) && ldb % 4 == 0;
-    rc = launch_lm<unsigned char, LM_BED>(ctx, lm_np(c, t) / 16, a, vec);
+    rc = launch_lm<unsigned char, GENO_BED>(ctx, lm_np(c, t) / 16, a, vec);
     if (rc) return rc;
     return pval ? lm_pvalues(ctx, n, c, t, pb, F, pval, ldo) : PG_OK;
 }

@@ -19,14 +19,12 @@
 // zero (groups of 16 in order, steps 0..3, the four k-groups inside the instruction), and the partials are added to score in ascending
 // chunk order by a second kernel over the partials that one workgroup per (chunk, 256 samples) left in the work area: split-K, no
 // atomics.  (A workgroup that walks its chunks itself gives the same bits and was slower at every size measured)
-#include "common.hpp"
+#include "geno_src.hpp"
 
 #include <cmath>
 #include <type_traits>
 
 namespace pg {
-
-enum { PRS_BED = 0, PRS_SAMPLE = 1, PRS_SNP = 2 };     // packed .bed records | (n x pb) sample-major | (pb x n) SNP-major
 
 constexpr int PRS_NT = 4;                               // 16-sample N-tiles per wavefront
 constexpr int PRS_WAVES = 4;
@@ -50,7 +48,6 @@ struct PrsArgs {
 
 static inline long long prs_chunks(long long pb) { return (pb + PG_PRS_CHUNK - 1) / PG_PRS_CHUNK; }
 static inline long long prs_groups(long long n) { return (n + PRS_ROWS - 1) / PRS_ROWS; }
-static inline size_t prs_up(size_t b) { return (b + 255) / 256 * 256; }
 
 struct PrsWork {
     long long *counts;     // [pb][4] the pre-pass's outputs
@@ -66,25 +63,25 @@ static PrsWork prs_work(void *work, long long n, long long pb, int t)
     char *b = static_cast<char *>(work);
     PrsWork w;
     size_t o = 0;
-    w.counts = reinterpret_cast<long long *>(b + o); o += prs_up((size_t)pb * 32);
-    w.moments = reinterpret_cast<double *>(b + o); o += prs_up((size_t)pb * 32);
-    w.ss = b + o; o += prs_up(pg_snp_stats_work_bytes(n, pb));
+    w.counts = reinterpret_cast<long long *>(b + o); o += up256((size_t)pb * 32);
+    w.moments = reinterpret_cast<double *>(b + o); o += up256((size_t)pb * 32);
+    w.ss = b + o; o += up256(pg_snp_stats_work_bytes(n, pb));
     const size_t part = (size_t)prs_chunks(pb) * t * ((n + 15) / 16 * 16);
-    w.ps = reinterpret_cast<double *>(b + o); o += prs_up(part * 8);
-    w.pc = reinterpret_cast<int *>(b + o); o += prs_up(part * 4);
+    w.ps = reinterpret_cast<double *>(b + o); o += up256(part * 8);
+    w.pc = reinterpret_cast<int *>(b + o); o += up256(part * 4);
     w.bytes = o + 256;
     return w;
 }
 
 // the four SNPs g .. g + 3 of sample i as they are stored; it: the first sample of i's N-tile.  SNPs >= pb and samples >= n are not read
 template <class T, int LAY> struct PrsRaw { T v[4]; };
-template <class T> struct PrsRaw<T, PRS_BED> { unsigned w[4]; };      // the N-tile's 16 two-bit calls of each SNP
+template <class T> struct PrsRaw<T, GENO_BED> { unsigned w[4]; };      // the N-tile's 16 two-bit calls of each SNP
 
 template <class T, int LAY>
 __device__ __forceinline__ void prs_load(PrsRaw<T, LAY> &r, const PrsArgs &a, long long g, long long i, long long it, bool vec)
 {
     const T *X = static_cast<const T *>(a.X);
-    if constexpr (LAY == PRS_BED) {
+    if constexpr (LAY == GENO_BED) {
         const long long bpr = ((long long)a.n + 3) / 4, b0 = it >> 2;
 #pragma unroll
         for (int s = 0; s < 4; s++) {
@@ -104,7 +101,7 @@ __device__ __forceinline__ void prs_load(PrsRaw<T, LAY> &r, const PrsArgs &a, lo
 #pragma unroll
         for (int s = 0; s < 4; s++) {
             const bool in = g + s < a.pb && i < a.n;
-            if constexpr (LAY == PRS_SNP) r.v[s] = in ? X[(g + s) * a.ldX + i] : T(0);
+            if constexpr (LAY == GENO_SNP) r.v[s] = in ? X[(g + s) * a.ldX + i] : T(0);
             else r.v[s] = in ? X[i * a.ldX + g + s] : T(0);
         }
     }
@@ -115,7 +112,7 @@ __device__ __forceinline__ void prs_load(PrsRaw<T, LAY> &r, const PrsArgs &a, lo
 template <class T, int LAY>
 __device__ __forceinline__ void prs_val(const PrsRaw<T, LAY> &r, int s, int c, bool in, double mu, int count_a1, double &x, double &m)
 {
-    if constexpr (LAY == PRS_BED) {
+    if constexpr (LAY == GENO_BED) {
         const unsigned code = (r.w[s] >> (2 * c)) & 3u;
         const bool call = in && code != 1u;
         x = call ? (code == 2u ? 1.0 : (((code == 3u) != (count_a1 != 0)) ? 2.0 : 0.0)) : (in ? mu : 0.0);
@@ -250,12 +247,6 @@ static int launch_prs(pg_ctx *ctx, const PrsArgs &a, bool vec)
     return PG_OK;
 }
 
-template <class T>
-static int launch_prs_x(pg_ctx *ctx, bool snp_major, const PrsArgs &a)
-{
-    return snp_major ? launch_prs<T, PRS_SNP>(ctx, a, false) : launch_prs<T, PRS_SAMPLE>(ctx, a, false);
-}
-
 // the argument checks the two entry points share (after their NULL checks); what: the entry's name
 static int prs_check(const char *what, int64_t n, int64_t pb, int t, int64_t ldw, int64_t lds)
 {
@@ -322,7 +313,7 @@ extern "C" int pg_prs_bed_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsi
     }
     const PrsArgs a = prs_args(n, pb, bed, ldb, count_a1 != 0, t, Wt, ldw, w, impute != 0, score, called, lds);
     const bool vec = ((uintptr_t)bed % 4 == 0) && ldb % 4 == 0;
-    return launch_prs<unsigned char, PRS_BED>(ctx, a, vec);
+    return launch_prs<unsigned char, GENO_BED>(ctx, a, vec);
 }
 
 extern "C" int pg_prs_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, int t, const double *Wt,
@@ -333,7 +324,7 @@ extern "C" int pg_prs_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *
     if (rc) return rc;
     PG_REQUIRE(ldX >= (snp_major ? n : pb), "pg_prs_x_acc_dev: ldX=%lld too small for n=%lld pb=%lld snp_major=%d", (long long)ldX, (long long)n,
                (long long)pb, snp_major);
-    if (dtype < PG_DTYPE_INT8 || dtype > PG_DTYPE_FLOAT64) {
+    if (!dtype_known(dtype)) {
         set_error("pg_prs_x_acc_dev: unknown dtype %d", dtype);
         return PG_ENOTSUP;
     }
@@ -346,11 +337,8 @@ extern "C" int pg_prs_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *
         if (rc) return prs_prepass_refused("pg_prs_x_acc_dev", rc);
     }
     const PrsArgs a = prs_args(n, pb, X, ldX, 0, t, Wt, ldw, w, prepass, score, called, lds);
-    const bool sm = snp_major != 0;
-    switch (dtype) {
-        case PG_DTYPE_INT8: return launch_prs_x<signed char>(ctx, sm, a);
-        case PG_DTYPE_UINT8: return launch_prs_x<unsigned char>(ctx, sm, a);
-        case PG_DTYPE_FLOAT32: return launch_prs_x<float>(ctx, sm, a);
-        default: return launch_prs_x<double>(ctx, sm, a);
-    }
+    return geno_dispatch(dtype, snp_major != 0, [&](auto src) {
+        using S = decltype(src);
+        return launch_prs<typename S::type, S::layout>(ctx, a, false);
+    });
 }

@@ -18,7 +18,7 @@
 // same elements arrive through scalar loads, in the same lanes.
 // Determinism: every floating-point sum is one fixed chain — a lane's elements in order, a fixed tree across lanes, wavefronts 0..3, chunks
 // 0..R-1 — that depends on n and the layout only: a row depends on its SNP alone, not on pb, the batch boundaries, the pitch or the run.
-#include "common.hpp"
+#include "geno_src.hpp"
 
 #include <cmath>
 #include <type_traits>
@@ -333,11 +333,11 @@ __global__ __launch_bounds__(256) void ss_sm_final_kernel(int n, long long pb, l
     }
 }
 
-template <class T>
-static int launch_ss_x(pg_ctx *ctx, int n, long long pb, const void *X, long long ldX, bool snp_major, void *work, long long *counts, double *moments)
+template <class T, int LAY>
+static int launch_ss_x(pg_ctx *ctx, int n, long long pb, const void *X, long long ldX, void *work, long long *counts, double *moments)
 {
     const T *Xt = static_cast<const T *>(X);
-    if (snp_major) {
+    if (LAY == GENO_SNP) {
         const bool vec = ((uintptr_t)X % 16 == 0) && ((size_t)ldX * sizeof(T)) % 16 == 0;
         static_assert(SS_MAXPB / 4 + 1 < SS_MAXGRID, "one wavefront per SNP");
         ss_snp_kernel<T><<<(unsigned)((pb + 3) / 4), 256, 0, ctx->stream>>>(n, pb, Xt, ldX, vec, counts, moments);
@@ -438,20 +438,17 @@ extern "C" int pg_snp_stats_x_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void
     PG_REQUIRE(ctx && X && work && counts && moments, "pg_snp_stats_x_dev: NULL argument");
     PG_REQUIRE(n >= 1 && n < (1LL << 30) && pb >= 0 && pb <= SS_MAXPB && ldX >= (snp_major ? n : pb),
                "pg_snp_stats_x_dev: bad shape n=%lld pb=%lld ldX=%lld snp_major=%d", (long long)n, (long long)pb, (long long)ldX, snp_major);
-    if (dtype < PG_DTYPE_INT8 || dtype > PG_DTYPE_FLOAT64) {
+    if (!dtype_known(dtype)) {
         set_error("pg_snp_stats_x_dev: unknown dtype %d", dtype);
         return PG_ENOTSUP;
     }
     if (pb == 0) return PG_OK;
     PG_HIP(hipSetDevice(ctx->device));
     long long *cnt = reinterpret_cast<long long *>(counts);
-    const bool sm = snp_major != 0;
-    switch (dtype) {
-        case PG_DTYPE_INT8: return launch_ss_x<signed char>(ctx, (int)n, pb, X, ldX, sm, work, cnt, moments);
-        case PG_DTYPE_UINT8: return launch_ss_x<unsigned char>(ctx, (int)n, pb, X, ldX, sm, work, cnt, moments);
-        case PG_DTYPE_FLOAT32: return launch_ss_x<float>(ctx, (int)n, pb, X, ldX, sm, work, cnt, moments);
-        default: return launch_ss_x<double>(ctx, (int)n, pb, X, ldX, sm, work, cnt, moments);
-    }
+    return geno_dispatch(dtype, snp_major != 0, [&](auto src) {
+        using S = decltype(src);
+        return launch_ss_x<typename S::type, S::layout>(ctx, (int)n, pb, X, ldX, work, cnt, moments);
+    });
 }
 
 extern "C" int pg_hwe_exact_dev(pg_ctx *ctx, int64_t n, int64_t p, const int64_t *counts, double *pval)
