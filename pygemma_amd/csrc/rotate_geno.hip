@@ -67,7 +67,7 @@ __device__ __forceinline__ float f16_to_f32(unsigned short b)
     return (float)h;
 }
 
-// max |U| as an int key (order-independent), then the power-of-two scale S: S*max|U| in (2^14, 2^15]
+// max |U| as an int key (order-independent), then the power-of-two scale S: S*max|U| in [2^14, 2^15)
 __global__ void absmax_kernel(long long n, long long ldU, const float *U, int *key)
 {
     int m = 0;
