@@ -809,6 +809,15 @@ __global__ __launch_bounds__(512, 1) void kin_geno_kernel(GenoParams gp) { geno_
 // LDS image, swizzle, DMA shapes and fragment reads are byte-for-byte those of the fp16 kernel).  The three digits of an output meet
 // in the epilogue, through the LDS the main loop has released: i32 accumulators -> LDS, then per output 65536 a2 + 256 a1 + a0 in
 // fp64 (exact), times dx_g * 2^(E_k - 22), plus v0_g * (U'1)_k, one rounding to float32 — and row-contiguous 340-byte stores.
+// A thread keeps one eigen column and walks its rows four at a time (i8_combine_half): column values in registers, row values in LDS,
+// no global load and no wait on vmcnt in the write pass's loop, no division, 32-bit address steps.  Measured (s_memtime stamps of whole
+// tiles, tools/geno_i8_stamps.py, profiles/rotate_i8_epilogue.json): the loop it replaces — one output per iteration, v0 / colsum / dx /
+// wscale fetched again for every output in two dependent round trips, each also waiting for the store before — took 43.6 k of a tile's
+// 259.6 k ticks (16.8 %); this one takes 13.5 k of 229.0 k (5.9 %: 4.4 k staging, 9.2 k combine and store).  The kernel executes 40.1 M
+// cycles per 100 000-SNP launch instead of 45.3 M, and the chip holds 2.03 GHz on it instead of 2.18 (the MFMA phases have less idle
+// time between them): 20.74 -> 19.54 ms, rotation stage 22.37 -> 21.07 ms per step; the association kernel behind it runs its unchanged
+// 69.3 M cycles at 2.22 GHz instead of 2.25, +0.27 ms (profiles/rotate_i8_epilogue_bench.json).  The staging writes (64 ds_write2_b32
+// per wave, four waves per half) sit at about twice what the LDS takes to accept their 131 KB and are left as they are.
 // Every stage now brings a new genotype tile (no second plane to reuse it for): the early waves stage the whole 32 KB tile of stage
 // s+1 during stage s (8 DMA instructions per wave, waited at the END of their MFMA phase), into the buffer whose last readers — the
 // late waves' memory phase of stage s-1 — finished one barrier earlier.
@@ -838,15 +847,75 @@ struct GenoI8Params {
     int cmode;
 };
 
+// One thread's share of a staged half of rotate_geno_i8_kernel's tile: eigen column ee (s = stg + rg * I8_LDW + ee) of the rows rg, rg + 6,
+// ... (nj of them; rp their {dx, v0}; dst their outputs, `step` floats apart), four rows a step: the LDS reads of the four rows go out
+// together, then the arithmetic, then the stores, which nothing ever waits for — the write pass has no global load in its loop.  The
+// accumulating pass loads the old values of a step BEFORE the stores of the step in front of it (vmcnt retires in issue order: a load
+// issued behind a store would wait for the store's acknowledgement).  LDS reads past a thread's last row stay inside the LDS allocation
+// (row 127 + 18 of 260 words, row entry 273 behind it) and feed values that are not stored; whole steps store unpredicated.
+constexpr int I8_LDW = 260, I8_RG = 6, I8_UN = 4;
+template <bool ACCUM>
+__device__ __forceinline__ void i8_combine_half(const int *s, const double2 *rp, float *dst, unsigned step, int nj, double ws, double cs)
+{
+    float old[I8_UN] = {};
+    if (ACCUM && nj > 0) {
+#pragma unroll
+        for (int k = 0; k < I8_UN; k++) old[k] = dst[(k < nj ? k : 0) * step];
+    }
+    auto rows4 = [&](int j) {
+        int a2[I8_UN], a1[I8_UN], a0[I8_UN];
+        double2 r[I8_UN];
+        float out[I8_UN];
+#pragma unroll
+        for (int k = 0; k < I8_UN; k++) {
+            a2[k] = s[k * I8_RG * I8_LDW]; a1[k] = s[k * I8_RG * I8_LDW + I8_EIG]; a0[k] = s[k * I8_RG * I8_LDW + 2 * I8_EIG];
+            r[k] = rp[k * I8_RG];
+        }
+#pragma unroll
+        for (int k = 0; k < I8_UN; k++) {
+            const double P = fma((double)a2[k], 65536.0, fma((double)a1[k], 256.0, (double)a0[k]));      // 65536 a2 + 256 a1 + a0: exact
+            const double base = ACCUM ? (double)old[k] : r[k].y * cs;
+            out[k] = (float)fma(r[k].x * ws, P, base);
+            asm volatile("" : "+v"(out[k]));         // all four here: the compiler otherwise sinks the last row, LDS reads and all, into the whole-step branch
+        }
+        if (ACCUM) {
+#pragma unroll
+            for (int k = 0; k < I8_UN; k++) old[k] = dst[(j + I8_UN + k < nj ? I8_UN + k : 0) * step];
+        }
+        if (j + I8_UN <= nj) {
+#pragma unroll
+            for (int k = 0; k < I8_UN; k++) dst[k * step] = out[k];
+        } else {      // the last, partial step: a row past the end repeats the store of the step's first row (no branch around a store:
+                      // the wait for the next old values stays a counted one that leaves the stores in flight)
+#pragma unroll
+            for (int k = 0; k < I8_UN; k++) dst[(j + k < nj ? k : 0) * step] = j + k < nj ? out[k] : out[0];
+        }
+        s += I8_UN * I8_RG * I8_LDW; rp += I8_UN * I8_RG; dst += I8_UN * step;
+    };
+    int j = 0;
+    if (ACCUM && nj > 0) { rows4(0); j = I8_UN; }      // peeled, so that every entry to the loop has a step's stores behind the four loads it waits for
+#pragma unroll 1
+    for (; j < nj; j += I8_UN) rows4(j);
+}
+
 #ifdef PG_GENO_STAMPS      // tools/geno_i8_stamps.py: s_memtime at the phase boundaries of stages 8 .. 23 of workgroup 0, waves 0 (early) and 4 (late)
-__device__ long long g_geno_stamps[2][16][6];
+// and, for the whole tile (slots 0 .. 5: kernel entry, end of the K loop, half 0 staged, half 0 combined and stored, half 1 staged, kernel
+// exit), of the 8 workgroups at 4/16 .. 11/16 of the launch — away from its ramp-up and its tail — behind the 192 stage stamps
+__device__ long long g_geno_stamps[2 * 16 * 6 + 8 * 2 * 6];
 #define GENO_STAMP(slot)                                                                                   \
     do {                                                                                                   \
         if (blockIdx.x == 0 && (wave & 3) == 0 && lane == 0 && kt >= 8 && kt < 24)                         \
-            g_geno_stamps[wave >> 2][kt - 8][slot] = (long long)__builtin_amdgcn_s_memtime();              \
+            g_geno_stamps[((wave >> 2) * 16 + kt - 8) * 6 + slot] = (long long)__builtin_amdgcn_s_memtime(); \
+    } while (0)
+#define GENO_TILE_STAMP(slot)                                                                              \
+    do {                                                                                                   \
+        const unsigned sq_ = gridDim.x / 16, sw_ = sq_ ? blockIdx.x / sq_ : 0;                             \
+        if (sq_ && blockIdx.x == sw_ * sq_ && sw_ >= 4 && sw_ < 12 && (threadIdx.x & 255) == 0)            \
+            g_geno_stamps[192 + ((sw_ - 4) * 2 + (threadIdx.x >> 8)) * 6 + slot] = (long long)__builtin_amdgcn_s_memtime(); \
     } while (0)
 #else
 #define GENO_STAMP(slot) do { } while (0)
+#define GENO_TILE_STAMP(slot) do { } while (0)
 #endif
 #ifndef PG_GENO_AUX
 #define PG_GENO_AUX 1      // cache-policy bits of the LDS-DMA loads (sc0 = 1, nt = 2): measured 0 / 1 / 2 / 3 -> rotation 24.9 / 24.6 / 37.3 / 37.7 ms per step (nt gives up the L2 reuse between the workgroups of an XCD)
@@ -857,6 +926,7 @@ __device__ long long g_geno_stamps[2][16][6];
 __global__ __launch_bounds__(512, 1) void rotate_geno_i8_kernel(GenoI8Params gp)
 {
     if (!run_cond(gp.cond, gp.cmode)) return;
+    GENO_TILE_STAMP(0);
     constexpr int TBUF = 256 * 128;
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     unsigned char *const Bs = lds, *const As = lds + 3 * TBUF;
@@ -1000,36 +1070,66 @@ __global__ __launch_bounds__(512, 1) void rotate_geno_i8_kernel(GenoI8Params gp)
         b0 = (b0 == 2) ? 0 : b0 + 1;
     }
     if (!late) __builtin_amdgcn_s_barrier();
-    // ---------------- epilogue: the three digits of each output meet through LDS (all staging buffers are free now)
+    GENO_TILE_STAMP(1);
+    // ---------------- epilogue: the three digits of each output meet through LDS (all staging buffers are free now), one half of the
+    // tile's rows at a time.  A thread keeps ONE eigen column (ee = tid % 85, of row group tid / 85: 6 x 85 = 510 threads; the lanes of a
+    // wave cover consecutive columns of a row) and walks the rows rg, rg + 6, ...: what depends on the column alone sits in registers,
+    // what depends on the row alone ({dx, v0} as fp64) in LDS behind the staged half — loaded by the waves that have nothing to stage.
     const bool accum = gp.v0 == nullptr;           // the indicator pass: Xr += delta_g * U'ind_g
-    constexpr int LDW = 260;                       // words per staged row: the 4 row groups of a store (rows 4 apart) x 16 columns fall on 64 different banks
+    constexpr int LDW = I8_LDW;                    // words per staged row: the 4 row groups of a store (rows 4 apart) x 16 columns fall on 64 different banks
     int *const stg = reinterpret_cast<int *>(lds);
-#pragma unroll 1
-    for (int half = 0; half < 2; half++) {
-        if ((wm >> 1) == half) {
-            const int rb = (wm & 1) * 64;
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 8; j++)
-#pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        stg[(rb + i * 16 + 4 * (lane >> 4) + e) * LDW + wn * 128 + j * 16 + (lane & 15)] = acc[i][j][e];
-        }
-        __syncthreads();
-        for (int idx = tid; idx < 128 * I8_EIG; idx += 512) {
-            const int rr = idx / I8_EIG, ee = idx - rr * I8_EIG;
-            const long long row = m0 + half * 128 + rr, col = k0 + ee;
-            if (row < gp.p && col < gp.n) {
-                const int *s = stg + rr * LDW + ee;
-                const double P = (double)s[0] * 65536.0 + (double)s[I8_EIG] * 256.0 + (double)s[2 * I8_EIG];     // exact
-                float *dst = gp.Xr + row * gp.ldx + col;
-                const double base = accum ? (double)(*dst) : (double)gp.v0[row] * gp.colsum[col];
-                *dst = (float)fma((double)gp.dx[row] * gp.wscale[col], P, base);
-            }
-        }
-        __syncthreads();
+    double2 *const rowv = reinterpret_cast<double2 *>(lds + 128 * LDW * 4);      // 256 x 16 B behind the 133 120 B of a staged half
+    const int rows = (int)((gp.p - m0) < 256 ? (gp.p - m0) : 256);               // rows of this tile inside the block
+    // every load below is unconditional, from a clamped index (a pointer that is always valid in the accumulating pass): nothing
+    // branches around a load, and no wait lands in front of the staging writes
+    const int rg = tid / I8_EIG, ee = tid - rg * I8_EIG;
+    const long long col = k0 + ee;
+    const bool colok = rg < I8_RG && col < gp.n;
+    const double ws = gp.wscale[col < gp.n ? col : gp.n - 1];
+    const double cs = (accum ? gp.wscale : gp.colsum)[col < gp.n ? col : gp.n - 1];
+    const int rrow = (tid & 255) < rows ? (tid & 255) : rows - 1;
+    float rdx = 0.0f, rv0 = 0.0f;
+    if (late) {
+        rdx = gp.dx[m0 + rrow];
+        rv0 = (accum ? gp.dx : gp.v0)[m0 + rrow];
     }
+    float *const dst = gp.Xr + (m0 + rg) * gp.ldx + col;                         // 64-bit once; the rows go by 32-bit steps from here
+    const unsigned step = (unsigned)(I8_RG * gp.ldx);
+    auto stage = [&]() {                             // the wave's 64 x 128 accumulators -> rows (wm & 1) * 64 .. of the staged half
+        const int rb = (wm & 1) * 64;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    stg[(rb + i * 16 + 4 * (lane >> 4) + e) * LDW + wn * 128 + j * 16 + (lane & 15)] = acc[i][j][e];
+    };
+    auto lds_barrier = [&]() {                       // raw: the global stores of the half before stay in flight across it
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto combine = [&](int half) {
+        const int hrows = rows - half * 128 < 128 ? rows - half * 128 : 128;
+        const int nj = (colok && rg < hrows) ? (hrows - rg + I8_RG - 1) / I8_RG : 0;      // this thread's rows of the half
+        float *const d = dst + (unsigned)half * (unsigned)(128 * gp.ldx);
+        if (accum) i8_combine_half<true>(stg + rg * LDW + ee, rowv + half * 128 + rg, d, step, nj, ws, cs);
+        else i8_combine_half<false>(stg + rg * LDW + ee, rowv + half * 128 + rg, d, step, nj, ws, cs);
+    };
+    if (!late) stage();                              // rows [0, 128) are the early waves'; the late ones bring the row values meanwhile
+    else rowv[tid - 256] = make_double2((double)rdx, (double)rv0);
+    asm volatile("" :: "v"(ws), "v"(cs));            // the column values have landed HERE on every path: no wait on vmcnt from here on can catch a store
+    lds_barrier();
+    GENO_TILE_STAMP(2);
+    combine(0);
+    lds_barrier();                                   // every LDS read of the first half has been consumed: the second may overwrite it
+    GENO_TILE_STAMP(3);
+    if (late) stage();
+    lds_barrier();
+    GENO_TILE_STAMP(4);
+    combine(1);
     if (tn == gp.tiles_n - 1) {                    // the pad columns [n, ldx) of the rotated rows are zero (the association kernel reads whole rows)
         const int padw = (int)(gp.ldx - gp.n);
         for (int idx = tid; idx < 256 * padw; idx += 512) {
@@ -1037,6 +1137,7 @@ __global__ __launch_bounds__(512, 1) void rotate_geno_i8_kernel(GenoI8Params gp)
             if (row < gp.p) gp.Xr[row * gp.ldx + gp.n + idx % padw] = 0.0f;
         }
     }
+    GENO_TILE_STAMP(5);
 }
 
 // per-eigenvector exponent and the three int8 digit planes of U (see rotate_geno_i8_kernel)
@@ -1470,6 +1571,10 @@ extern "C" int pg_rotate_bed_dev(pg_ctx *ctx, int64_t n, int64_t p, const void *
 extern "C" int pgx_geno_stamps(long long *out192)
 {
     return hipMemcpyFromSymbol(out192, HIP_SYMBOL(pg::g_geno_stamps), sizeof(long long) * 192) == hipSuccess ? 0 : -1;
+}
+extern "C" int pgx_geno_tile_stamps(long long *out96)      // [workgroup 0 .. 7][wave 0, wave 4][slot 0 .. 5]
+{
+    return hipMemcpyFromSymbol(out96, HIP_SYMBOL(pg::g_geno_stamps), sizeof(long long) * 96, sizeof(long long) * 192) == hipSuccess ? 0 : -1;
 }
 #endif
 
