@@ -308,6 +308,47 @@ int pg_prs_bed_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *
 int pg_prs_x_acc_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, int t, const double *Wt,
                      int64_t ldw, int impute, void *work, double *score, int64_t *called, int64_t lds);
 
+/* ---- Principal components from RAW genotypes on the fp64 matrix pipe (csrc/pca.hip): the two skinny products of a
+ * randomised block subspace iteration against the standardised genotypes Z (pb x n), T = Z'Q and Y += Z T.  Block conventions of
+ * pg_prs_*_acc_dev / pg_snp_stats_*_dev: an (n x pb) sample-major (snp_major = 0, ldX >= pb) or (pb x n) SNP-major (ldX >= n) block of
+ * dtype PG_DTYPE_*, or pb packed .bed records (ldb >= ceil(n/4) bytes; code convention and count_a1 of pg_rotate_bed_dev).  An element is
+ * first rounded to float32; missing is .bed code 01 or a non-finite float element (an 8-bit block has no missing code); pad bits and
+ * pad elements never reach a result and are never read.
+ *   stat    : pb x 2 doubles {mu_g, isd_g}.  pg_pca_stat_* runs pg_snp_stats_*_dev over the block as a pre-pass and writes mu_g = the
+ *             mean it reports, bit for bit (0 for a SNP without a called sample), and with v = var_g ((double)n_obs / (double)n)
+ *             isd_g = v > 0 ? 1.0 / sqrt(v) : 0.0 (IEEE division and square root): the population sd over all n samples after mean
+ *             imputation, lmm.kinship(standardize=True)'s; a constant or all-missing SNP contributes zeros.  A row depends only on
+ *             its SNP.  stat is an INPUT of proj and back: new samples are projected with the training panel's moments.
+ *   values  : z_gi = fl(fl(x_gi - mu_g) isd_g), two fp64 roundings; 0 for a missing call, a sample >= n and a SNP >= pb.
+ *   Q, Y, T : component-major, like the scores of pg_prs: component k of sample i at Q[k ldq + i] (ldq >= n), of SNP g at T[k ldt + g]
+ *             (ldt >= pb); l <= PG_PCA_MAX_L components.  The output of back is the input of proj.
+ *   proj    : T[k][g] = sum_i z_gi Q[k][i] on v_mfma_f64_16x16x4_f64 with the samples as K.  An output is one fixed chain that depends
+ *             only on the SNP, its stat and Q — not on the SNP's slot, tile, batch, pitch, alignment or storage; no split over samples,
+ *             no atomics.  Nothing outside [k ldt, k ldt + pb), k < l, is written.
+ *   back    : Y[k][i] += sum_g z_gi T[k][g] (the caller zeroes Y before the first batch), the SNPs as K.  The ordering contract of
+ *             pg_prs_*_acc_dev: the block's SNPs are cut into chunks of PG_PCA_CHUNK from its first SNP; a chunk's partial is accumulated
+ *             from zero in an order that depends only on the position inside the chunk; a second kernel adds the partials to Y in
+ *             ascending chunk order; no floating-point atomics.  Y does not depend on the batch sizes when every batch but the last
+ *             holds a multiple of PG_PCA_CHUNK SNPs.  Nothing outside [k ldy, k ldy + n), k < l, is written.
+ *   work    : device scratch of pg_pca_work_bytes(n, pb, l) bytes: the pre-pass's outputs (stat; any l will do) and the per-chunk
+ *             partials (back: 8 l n bytes per chunk); 0 for a refused shape.
+ * PG_EINVAL for NULL pointers, n < 1, n >= 2^30, pb < 0, pb > 2^25, l < 1, strides too small, a block of 2^31 or more workgroups
+ * (ceil(n / 256) sample groups x ceil(pb / 256) chunks) or a pre-pass that pg_snp_stats_x_dev refuses; PG_ENOTSUP for l > PG_PCA_MAX_L or
+ * an unknown dtype: a refused call enqueues nothing.  pb = 0 is a no-op. */
+#define PG_PCA_CHUNK 256      /* SNPs per summation chunk of the back-product */
+#define PG_PCA_MAX_L 64       /* columns of the iterated block: four 16-column tiles */
+size_t pg_pca_work_bytes(int64_t n, int64_t pb, int l);      /* 0 for a refused shape */
+int pg_pca_stat_bed_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, void *work, double *stat);
+int pg_pca_stat_x_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, void *work, double *stat);
+int pg_pca_proj_bed_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, const double *stat, int l,
+                        const double *Q, int64_t ldq, double *T, int64_t ldt);
+int pg_pca_proj_x_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, const double *stat, int l,
+                      const double *Q, int64_t ldq, double *T, int64_t ldt);
+int pg_pca_back_bed_dev(pg_ctx *ctx, int64_t n, int64_t pb, const unsigned char *bed, int64_t ldb, int count_a1, const double *stat, int l,
+                        const double *T, int64_t ldt, void *work, double *Y, int64_t ldy);
+int pg_pca_back_x_dev(pg_ctx *ctx, int64_t n, int64_t pb, const void *X, int dtype, int64_t ldX, int snp_major, const double *stat, int l,
+                      const double *T, int64_t ldt, void *work, double *Y, int64_t ldy);
+
 /* ---- SNP-by-environment interaction (GEMMA's -gxe): for SNP g with rotated genotype x = U'x_g and rotated interaction
  * xe = U'(x_g o e), the REML Wald test of xe in  y ~ W' + x + xe,  W' = the c shared covariates (the caller's W and U'e).
  * Row g is by definition calculate(d, yr, [W', x], xe) of pg_assoc_dev's arithmetic with c + 1 covariates (decade scan,

@@ -42,7 +42,7 @@ from . import model as _model
 
 __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
            "kinship", "ld", "ld_window", "ld_prune", "clump", "prs", "prs_weights", "king", "ibs", "sample_stats", "related_pairs",
-           "unrelated"] + _model.__all__
+           "unrelated", "pca", "pca_project", "PcaResult"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -1419,6 +1419,230 @@ def prs_weights(df, loci=None, thresholds=(5e-8, 1e-5, 1e-3, 1e-2, 0.05, 1.0), c
     with np.errstate(invalid="ignore"):
         cols = [np.where(keep & (pv <= thr), b, 0.0) for thr in thresholds]
     return pd.DataFrame(np.stack(cols, axis=1) if cols else np.zeros((p, 0)), columns=list(thresholds), index=df.index)
+
+
+_PCA_MAX_L = 64      # PG_PCA_MAX_L: columns of the iterated block
+_PCA_RESIDENT_BATCH = 65536      # SNPs per kernel call from a resident source: 512 strips of 128 SNPs for proj, two per compute unit
+PcaResult = namedtuple("PcaResult", "pcs eigenvalues explained loadings stat")
+
+
+def _pca_orth(A):
+    """The orthonormal factor of the host fp64 Householder QR of A (n, l), with the diagonal of R made positive."""
+    Q, R = np.linalg.qr(A)
+    return Q * np.where(np.diagonal(R) < 0, -1.0, 1.0)[None, :]
+
+
+def _pca_signs(U):
+    """Every column of U with its entry of largest magnitude made positive."""
+    U = np.array(U)
+    for j in range(U.shape[1]):
+        if U[np.argmax(np.abs(U[:, j])), j] < 0:
+            U[:, j] = -U[:, j]
+    return U
+
+
+class _PcaPanel:
+    """The genotypes of lmm.pca / lmm.pca_project on one GPU, for any number of passes of pg_pca_{stat,proj,back}_*: uploaded once and
+    read from HBM in windows (`resident`: the source, stat, T, the panels and the work area fit into 0.9 of the free memory and no
+    `snp_batch` was given), or streamed through a two-slot feed of its own per pass.  Either way a pass takes the SNPs in batches that
+    are multiples of the summation chunk, so the bits are the same.  stat (p, 2) and T (l, p) stay on the device; Q and Y are (l, n)."""
+
+    def __init__(self, ctx, X, l, snp_batch, who):
+        L = self.L = _lib.load()
+        src = self.src = _describe(X)
+        self.ctx, self.l, self.passes = ctx, l, 0
+        n, p = src.n, src.p
+        fixed = 16 * p + 8 * l * p + 16 * l * n
+        default = _chunk_up(_lm_batch(src))
+        free, _total = ctx.mem_info()
+        # from HBM a kernel call takes up to _PCA_RESIDENT_BATCH SNPs, halved down to the feed's batch while the chunk partials do not fit
+        # (a sample-major source lies there batch by batch as the feed would put it, so its calls keep the upload's size)
+        pbr = max(default, _PCA_RESIDENT_BATCH) if src.snp_major else default
+        need = lambda pb: fixed + p * src.row_bytes + int(L.pg_pca_work_bytes(n, min(p, pb), l))      # noqa: E731
+        while pbr > default and need(pbr) > 0.9 * free:
+            pbr = max(default, pbr // 2)
+        self.resident = snp_batch is None and need(pbr) <= 0.9 * free
+        if self.resident:
+            pb = min(p, pbr)
+        else:
+            pb = _fit_batch(ctx, None if snp_batch is None else _chunk_up(snp_batch), default, p, _PRS_CHUNK,
+                            lambda pb: fixed + 2 * pb * src.row_bytes + int(L.pg_pca_work_bytes(n, pb, l)),
+                            f"{who}: n={n}, p={p}, l={l}", "stat, T, two panels, two batch slots, the pre-pass and the chunk partials")
+            if pb < p:
+                pb = max(_PRS_CHUNK, pb // _PRS_CHUNK * _PRS_CHUNK)
+        self.pb = pb
+        self.work = ctx.alloc(L.pg_pca_work_bytes(n, pb, l))
+        self.dstat, self.dT, self.dQ, self.dY = ctx.alloc(16 * p), ctx.alloc(8 * l * p), ctx.alloc(8 * l * n), ctx.alloc(8 * l * n)
+        self.dX = None
+        if self.resident:      # every batch where the feed would put it: SNP-major rows back to back, a sample-major window as n x (e - s)
+            self.dX = ctx.alloc(p * src.row_bytes)
+            up = min(p, default)
+            ring = _Ring(ctx, up * src.row_bytes, staged=not src.direct)
+            try:
+                for j, s in enumerate(range(0, p, up)):
+                    e = min(s + up, p)
+                    ring.put(j, src.src, s, e, self.dX.ptr + s * src.row_bytes, None if src.snp_major else (e - s) * src.esz)
+                ctx.sync()
+            finally:
+                ring.close()
+
+    @contextlib.contextmanager
+    def _batches(self):
+        src, pb = self.src, self.pb
+        self.passes += 1
+        if self.resident:
+            yield ((s, min(s + pb, src.p), self.dX.ptr + s * src.row_bytes) for s in range(0, src.p, pb))
+        else:
+            with contextlib.closing(_Feed(self.ctx, src)) as feed:
+                yield feed.batches(pb)
+
+    def sweep(self, stat=False, proj=0, back=0):
+        """One pass over the SNPs: per batch its stat, then T = Z'Q for the first `proj` rows of dQ, then dY += Z T for the first `back`
+        rows of dT.  Returns Y (back, n) from the device, or None."""
+        L, ctx, src = self.L, self.ctx, self.src
+        n, p = src.n, src.p
+        if back:
+            _lib.check(L.pg_memset(ctx.handle, self.dY.ptr, 0, 8 * back * n), "pg_memset")
+        with self._batches() as batches:
+            for s, e, slot in batches:
+                head, st = (ctx.handle, n, e - s), self.dstat.ptr + 16 * s
+                if stat:
+                    _call_dev(L, "pg_pca_stat_{}_dev", src, head, slot, e - s, (self.work.ptr, st))
+                if proj:
+                    _call_dev(L, "pg_pca_proj_{}_dev", src, head, slot, e - s, (st, proj, self.dQ.ptr, n, self.dT.ptr + 8 * s, p))
+                if back:
+                    _call_dev(L, "pg_pca_back_{}_dev", src, head, slot, e - s, (st, back, self.dT.ptr + 8 * s, p, self.work.ptr, self.dY.ptr, n))
+            ctx.sync()
+        return self.dY.download((back, n), np.float64) if back else None
+
+    def stream_stats(self, stats, t0, **more):
+        if stats is not None:
+            nb = -(-self.src.p // self.pb)
+            stats.update({"resident": self.resident, "batches": nb * self.passes,
+                          "bytes_in": self.src.p * self.src.row_bytes * (1 if self.resident else self.passes), "seconds": time.time() - t0, **more})
+
+
+def _pca_source(X, who, samples, snps=None):
+    X = _genotypes(X, who)
+    n, p = X.shape
+    if n < 1 or p < 1:
+        raise ValueError(f"{who} needs at least one sample and one SNP: X holds n={n}, p={p}")
+    if samples is not None and len(samples) != n:
+        raise ValueError(f"shape mismatch: {len(samples)} sample labels for {n} samples")
+    if snps is not None and len(snps) != p:
+        raise ValueError(f"shape mismatch: {len(snps)} SNP names for {p} SNPs")
+    return X, n, p
+
+
+def pca(X, k=10, *, oversample=10, iters=12, tol=1e-10, seed=0, loadings=True, samples=None, snps=None, device=0, snp_batch=None, verbose=0,
+        stats=None):
+    """The top k principal components of the standardised genotypes — the covariates W of every scan here (plink2's --pca approx) —
+    straight from the genotypes as they are stored, without the n x n kinship matrix and its eigensolver: randomised block subspace
+    iteration with two skinny fp64 products per pass on the matrix pipe (csrc/pca.hip).
+
+    X (n, p): whatever prs takes — a PackedBed, or an int8, uint8, float32 or float64 array in C or Fortran order, pinned or pageable.
+    Values are snp_stats' (rounded to float32 per element; .bed code 01, NaN and +-Inf are missing, an 8-bit array has no missing
+    code).  Z is lmm.kinship(standardize=True)'s: z_gi = (x_gi - mu_g) / sd_g with mu_g the mean of the called genotypes — the number
+    snp_stats reports — sd_g the population sd over all n samples after mean imputation, and 0 for a missing call; a constant or
+    all-missing SNP contributes zeros and still counts in p.  The eigenvalues are those of K = Z Z' / p.
+    With l = min(k + oversample, 64, n):  Q = orth(default_rng(seed).standard_normal((n, l)));  per pass T = Z'Q, Y = Z T / p,
+    B = sym(Q'Y) and its Ritz values by host eigh; stop when the top k moved less than `tol` relative to the largest, or after `iters`
+    passes; otherwise Q = orth(Y).  orth is a host fp64 Householder QR with R's diagonal made positive.  pcs = Q V[:, :k], each column's
+    entry of largest magnitude positive.  With `loadings` one more product gives L = Z' pcs / (p lambda), so that Z L = pcs for a
+    converged component (pca_project).  Axes of ancestry, which have an eigenvalue gap, converge to rounding in a dozen passes; components
+    inside the bulk of the spectrum have none and stay a few percent short (stats["converged"] says which case it was).
+    Returns a PcaResult: pcs (n x k DataFrame PC1..PCk, indexed by `samples`), eigenvalues (k,), explained = eigenvalues / trace K
+    (trace K = n p_used / p, p_used the SNPs with sd > 0), loadings (p x k DataFrame indexed by `snps`, or None) and stat (p, 2): mu_g
+    and 1 / sd_g (0 for an unusable SNP).  Use it as  W = np.c_[np.ones(n), res.pcs]  in lmm.pygemma.
+    When the source, stat, T and the work area fit into the free device memory and `snp_batch` is None, X is uploaded once and every
+    pass runs from HBM; otherwise every pass streams through the two-slot feed in batches rounded up to 256 SNPs: the returned bits
+    are the same.  `stats` receives resident, passes, converged, batches, bytes_in, seconds and seconds_orth (download, QR and upload
+    of the n x l panel).  Single GPU.  Refused with ValueError before any device work: k < 1, k + oversample > 64, k > min(n, p),
+    iters < 1, tol < 0, X not 2-D, empty or of another dtype, label lengths that do not match, a bad snp_batch; RuntimeError when no
+    SNP is usable."""
+    _check_snp_batch(snp_batch)
+    for name, v, lo in (("k", k, 1), ("oversample", oversample, 0), ("iters", iters, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f"{name} must be an integer >= {lo}, not {v!r}")
+    if k + oversample > _PCA_MAX_L:
+        raise ValueError(f"pca iterates k + oversample <= {_PCA_MAX_L} columns, got k = {k}, oversample = {oversample}")
+    if not tol >= 0:
+        raise ValueError(f"tol must be >= 0, not {tol!r}")
+    X, n, p = _pca_source(X, "pca", samples, snps)
+    if k > min(n, p):
+        raise ValueError(f"k = {k} components of a panel of n={n}, p={p}: at most min(n, p)")
+    k, l, t0, t_orth = int(k), int(min(k + oversample, _PCA_MAX_L, n)), time.time(), 0.0
+    Q = _pca_orth(np.random.default_rng(seed).standard_normal((n, l)))
+    _gpus()
+    with _lib.Context(device) as ctx:
+        panel = _PcaPanel(ctx, X, l, snp_batch, "pca")
+        panel.sweep(stat=True)
+        stat = panel.dstat.download((p, 2), np.float64)
+        p_used = int((stat[:, 1] > 0).sum())
+        if p_used == 0:
+            raise RuntimeError("pca: no SNP is usable (every SNP is constant or all missing)")
+        prev, converged, done = None, False, 0
+        for it in range(int(iters)):
+            t1 = time.time()
+            panel.dQ.upload(np.ascontiguousarray(Q.T))
+            t_orth += time.time() - t1
+            Yt = panel.sweep(proj=l, back=l)
+            t1 = time.time()
+            Y = np.ascontiguousarray(Yt.T) / p
+            t_orth += time.time() - t1
+            B = Q.T @ Y
+            w, V = np.linalg.eigh((B + B.T) / 2)
+            w, V = w[::-1], V[:, ::-1]
+            done = it + 1
+            _log(verbose - 1, f"pca: pass {done}, Ritz values {w[:k]}")
+            if prev is not None and np.max(np.abs(w[:k] - prev[:k])) < tol * abs(w[0]):
+                converged = True
+                break
+            prev = w
+            if it + 1 < iters:
+                t1 = time.time()
+                Q = _pca_orth(Y)
+                t_orth += time.time() - t1
+        pcs, lam = _pca_signs(Q @ V[:, :k]), w[:k].copy()
+        Lm = None
+        if loadings:
+            panel.dQ.upload(np.ascontiguousarray(pcs.T))
+            panel.sweep(proj=k)
+            Lm = panel.dT.download((l, p), np.float64)[:k].T / (p * lam)[None, :]
+        panel.stream_stats(stats, t0, passes=done, converged=converged, seconds_orth=t_orth)
+    cols = [f"PC{j + 1}" for j in range(k)]
+    _log(verbose, f"PCA: {k} components of {p} SNPs x {n} individuals in {done} passes, {time.time() - t0:.3f} s")
+    return PcaResult(pd.DataFrame(pcs, columns=cols, index=None if samples is None else pd.Index(samples)), lam, lam / (n * p_used / p),
+                     None if Lm is None else pd.DataFrame(Lm, columns=cols, index=None if snps is None else pd.Index(snps)), stat)
+
+
+def pca_project(X_new, res, *, samples=None, device=0, snp_batch=None, verbose=0, stats=None):
+    """The samples of X_new (n_new, p) on the components of res = lmm.pca(..., loadings=True): Z_new L as an n_new x k DataFrame PC1..PCk
+    indexed by `samples`.  X_new is standardised with res.stat — the TRAINING panel's means and sds, so a missing call is the training
+    mean — and the product is one stream of pg_pca_back_* (chunks of 256 SNPs added in order: the bits do not depend on `snp_batch`).
+    On the training panel itself it reproduces res.pcs for a converged component.  `stats` receives resident, batches, bytes_in,
+    seconds.  Refused with ValueError before any device work: a result without loadings, X_new with another SNP count, not 2-D, empty
+    or of another dtype, `samples` of another length, a bad snp_batch."""
+    _check_snp_batch(snp_batch)
+    if getattr(res, "loadings", None) is None:
+        raise ValueError("pca_project needs the loadings of lmm.pca(..., loadings=True)")
+    X_new, n, p = _pca_source(X_new, "pca_project", samples)
+    Lm, stat = np.asarray(res.loadings, np.float64), np.ascontiguousarray(res.stat, np.float64)
+    if Lm.ndim != 2 or Lm.shape[0] != p or stat.shape != (p, 2):
+        raise ValueError(f"shape mismatch: X_new holds {p} SNPs, the result's loadings {Lm.shape[0]} and its stat {stat.shape[0]}")
+    k, t0 = Lm.shape[1], time.time()
+    if not 1 <= k <= _PCA_MAX_L:
+        raise ValueError(f"pca_project takes 1 to {_PCA_MAX_L} components, got {k}")
+    _gpus()
+    with _lib.Context(device) as ctx:
+        panel = _PcaPanel(ctx, X_new, k, snp_batch, "pca_project")
+        panel.dstat.upload(stat)
+        panel.dT.upload(np.ascontiguousarray(Lm.T))
+        P = panel.sweep(back=k).T
+        panel.stream_stats(stats, t0)
+    _log(verbose, f"PCA projection: {n} individuals x {p} SNPs on {k} components in {time.time() - t0:.3f} s")
+    return pd.DataFrame(P, columns=list(res.loadings.columns) if isinstance(res.loadings, pd.DataFrame) else [f"PC{j + 1}" for j in range(k)],
+                        index=None if samples is None else pd.Index(samples))
 
 
 def _zkzt(L, Z, K):
