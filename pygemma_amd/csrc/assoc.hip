@@ -17,7 +17,9 @@
 // What is shared between SNPs is hoisted: the decade lambdas 10^-5..10^5 are the same for every SNP,
 // so h tables, the SNP-independent Gram entries (W,y block), trace terms and log|H| at those 11
 // lambdas are computed once (setup kernel); per SNP the scan only accumulates the 2(c+2) entries
-// that involve x.  Evaluations at SNP-specific lambdas (Brent, Newton, final) need the full Grams.
+// that involve x, and of the sweeps at those lambdas the c covariate pivots on the (W,y) block are the
+// setup kernel's too (the decade table): a SNP updates its x row only, several lambdas side by side on
+// the lanes (decade_lanes).  Evaluations at SNP-specific lambdas (Brent, Newton, final) need the full Grams.
 #include "common.hpp"
 
 #include <cmath>
@@ -72,6 +74,15 @@ constexpr int WPB = PG_ASSOC_WPB;
 #ifndef PG_REUSE_MAX_SLOTS
 #define PG_REUSE_MAX_SLOTS 4      // ... while a lane owns at most this many Gram entries per power (c <= 20): 9 KiB of LDS per wave at 4
 #endif
+// Work repeated for nothing:
+#ifndef PG_ASSOC_DECADE_HOIST
+#define PG_ASSOC_DECADE_HOIST 1   // the covariate pivots of the decade sweeps once per call (setup_tabs_kernel), the x rows of the decades side by side on the lanes
+#endif
+
+// The decade table, per lambda — ONE definition for setup_tabs_kernel, decade_lanes and the host's allocation: c (c + 2) records of 4
+// doubles {ia, ba2, P(r_k, q), Q(r_k, q)} [step q][x-row entry k], then 8 doubles {trP, ld, P(y,y), Q(y,y) after the c covariate
+// pivots, t1, log|H|, lambda, 0}.
+__host__ __device__ constexpr size_t assoc_dtab_doubles(int c) { return (size_t)c * (c + 2) * 4 + 8; }
 
 // Per-wave dynamic LDS of assoc_kernel — ONE definition for the kernel's carve-up and the host's launch size, so the two
 // cannot drift apart: [piv: 3 M doubles when the sweeps exchange their pivot column through LDS] | [sav: Brent's last two
@@ -93,6 +104,7 @@ struct AssocParams {
     double *fixg;          // [NLAM][2][NP]  level-0 P,Q over all columns with x := 0
     double *t1tab;         // [NLAM]
     float *ldHtab;         // [NLAM]
+    double *dtab;          // [NLAM][assoc_dtab_doubles(c)]  the decade table (0: not built; the callers whose kernels sweep every decade themselves)
     float lam11[NLAM];
     float logl_c;          // f32(f32(.5nu*ln(.5nu/pi)) - .5nu)   (pyx:1821-1822)
     const int *leaf, *node, *level, *chunk;
@@ -383,19 +395,23 @@ __device__ __forceinline__ void wave_lds_sync();
 // PW: the powers swept (PW_P, PW_PQ or PW_PQR).  Every power's update reads itself and the lower powers only, and the pivots,
 // their logs and the clamps of P are P's own: sweeping fewer powers leaves the bits of those swept as they are.  PW_P exports
 // yPy, ld, Pxx_c, Pyx_c and sh; the fields of a power that is not swept are 0 and must not be read.
-template <int C, int PW>
+// REC (setup_tabs_kernel, PW_PQ): the sweeps stop after the C covariate pivots and leave in rec what decade_lanes applies to a SNP's
+// x row — per step q and x-row entry k the record {ia, ba2, P(r_k, q), Q(r_k, q)} (r_k = k, the (y, x) entry reads row y; zeros
+// where the entry is not updated at that step), then {trP, ld, P(y,y), Q(y,y)} after the C steps.  Nothing of o is set.
+template <int C, int PW, bool REC = false>
 __device__ __forceinline__ void lane_sweeps(double (&P)[Shape<C>::SLOTS], double (&Q)[Shape<C>::SLOTS], double (&R)[Shape<C>::SLOTS],
-                                            const Own<C> &own, double t1, double t2, int lane, EvalOut &o, double *piv)
+                                            const Own<C> &own, double t1, double t2, int lane, EvalOut &o, double *piv, double *rec = nullptr)
 {
     constexpr int M = Shape<C>::M, NP = Shape<C>::NP, SLOTS = Shape<C>::SLOTS;
     static_assert(PW == PW_P || PW == PW_PQ || PW == PW_PQR, "powers");
+    static_assert(!REC || PW == PW_PQ, "the decade table holds P and Q");
     constexpr bool DQ = (PW & 2) != 0, FULL = (PW & 4) != 0;
     // With three or more slots per lane (c >= 14) the pivot column goes through the wave's LDS (piv: 3 M doubles) instead of
     // lane shuffles: a shuffle-gather costs SLOTS permutes per operand, 6 SLOTS^2 per step — pure data movement either way.
     constexpr bool VIA_LDS = Shape<C>::SWEEP_LDS;
     if (own.valid[0] && own.e[0] == 0) P[0] = dmaxf(P[0], PG_MINV);
     double trP = t1, trPP = t2, apiv = 1.0;
-    for (int i = 1; i < M; i++) {
+    for (int i = 1; i < (REC ? M - 1 : M); i++) {
         const int q = i - 1, eqq = tri(q, q);
         double a, b = 0.0, e = 0.0;
         double ur[SLOTS], uc[SLOTS], vr[SLOTS], vc[SLOTS], wr[SLOTS], wc[SLOTS];
@@ -436,6 +452,14 @@ __device__ __forceinline__ void lane_sweeps(double (&P)[Shape<C>::SLOTS], double
         }
         if (lane == q) apiv = a;
         const double a2 = a * a, ia = -1.0 / a, ba2 = b / a2;
+        if constexpr (REC) {   // column q is not updated at its own step: every location is written once (replicas write the same value)
+            double *rq = rec + (size_t)q * M * 4;
+            if (lane < M) { rq[4 * lane] = ia; rq[4 * lane + 1] = ba2; }
+            if (lane <= q) { rq[4 * lane + 2] = 0.0; rq[4 * lane + 3] = 0.0; }
+#pragma unroll
+            for (int sl = 0; sl < SLOTS; sl++)
+                if (own.valid[sl] && own.c[sl] == q && own.r[sl] > q) { rq[4 * own.r[sl] + 2] = P[sl]; rq[4 * own.r[sl] + 3] = Q[sl]; }
+        }
         if constexpr (FULL) {
             const double ba = b / a;
             trPP = (trPP + ba * ba) - 2 * (e / a);
@@ -480,7 +504,13 @@ __device__ __forceinline__ void lane_sweeps(double (&P)[Shape<C>::SLOTS], double
     // at once (lane q holds pivot q), the f32 accumulation stays sequential
     const double lg = log(apiv);
     float ld = 0.0f;
-    for (int q = 0; q < M - 1; q++) ld = (float)((double)ld + __shfl(lg, q, 64));
+    for (int q = 0; q < (REC ? M - 2 : M - 1); q++) ld = (float)((double)ld + __shfl(lg, q, 64));
+    if constexpr (REC) {
+        const double pyy = gather<SLOTS>(P, NP - 1), qyy = gather<SLOTS>(Q, NP - 1);
+        double *tail = rec + (size_t)C * M * 4;
+        if (lane == 0) { tail[0] = trP; tail[1] = (double)ld; tail[2] = pyy; tail[3] = qyy; }
+        return;
+    }
     o.yPy = (float)gather<SLOTS>(P, NP - 1);
     o.yPPy = DQ ? (float)gather<SLOTS>(Q, NP - 1) : 0.0f;
     o.yPPPy = FULL ? (float)gather<SLOTS>(R, NP - 1) : 0.0f;
@@ -719,6 +749,18 @@ __global__ __launch_bounds__(64) void setup_tabs_kernel(AssocParams pr)
         }
     float ldH = device_logdet_H(pr, lam, lane, smem_f);
     if (lane == 0) { pr.t1tab[t] = t1; pr.ldHtab[t] = ldH; }
+    // the decade table: the C covariate pivots on the block [W | y] by lane_sweeps' own statements (the x row is 0 here and is not
+    // recorded), and the scalars of this lambda decade_lanes reads per lane
+    if constexpr (PG_ASSOC_DECADE_HOIST && C >= 1) {
+        __shared__ double piv_s[Shape<C>::SWEEP_LDS ? 3 * Shape<C>::M : 1];
+        if (pr.dtab) {
+            double *rec = pr.dtab + (size_t)t * assoc_dtab_doubles(C);
+            EvalOut e;
+            lane_sweeps<C, PW_PQ, true>(P, Q, R, own, t1, 0.0, lane, e, piv_s, rec);
+            double *tail = rec + (size_t)C * Shape<C>::M * 4;
+            if (lane == 0) { tail[4] = t1; tail[5] = (double)ldH; tail[6] = (double)lam; tail[7] = 0.0; }
+        }
+    }
 }
 
 // scan accumulation: only the Gram entries that involve x, for GG decade lambdas at once; the totals go to
@@ -967,12 +1009,83 @@ __device__ __forceinline__ float newton_dev(const AssocParams &pr, float lroot, 
     return lroot;
 }
 
+#if defined(PG_ASSOC_STAMPS) && !defined(PG_ASSOC_PART)   // tools/assoc_decade_stamps.py: s_memtime at wave entry, before and after the
+// decade sweeps and at wave exit, for 1024 SNPs spread evenly over the launch (this unit's kernels only: Wald, c <= 15)
+__device__ long long g_assoc_stamps[1024 * 4];
+#define ASSOC_STAMP(slot)                                                                                       \
+    do {                                                                                                        \
+        const long long sq_ = pr.p >= 1024 ? pr.p / 1024 : 1, sr_ = g / sq_;                                    \
+        if (lane == 0 && sr_ < 1024 && g == sr_ * sq_)                                                          \
+            g_assoc_stamps[sr_ * 4 + slot] = (long long)__builtin_amdgcn_s_memtime();                           \
+    } while (0)
+#else
+#define ASSOC_STAMP(slot) do { } while (0)
+#endif
+
+// The sweeps at the 11 decade lambdas, side by side on the lanes.  At a decade lambda the block [W | y] of P and Q is the same for every
+// SNP, and an update of entry (r, c) on the pivot q reads (r, q), (c, q) and the pivot only: the C covariate pivots, their
+// reciprocals, trP and the first C terms of ld are setup_tabs_kernel's (the decade table), and a SNP owns just its x row — the xent
+// entries k < C: (x, w_k), C: (x, x), C + 1: (y, x).  Lane (g, k) of 64 / M lambdas per round holds P and Q of entry k and applies
+// step q with the operand roles lane_sweeps gives that entry (ur, vr: the entry's row at column q; uc, vc: its column's), the x
+// row's own (x, q) by one shuffle inside the lambda's lanes; then every lane of the lambda does the pivot on x — (y, y), trP, the
+// last term of ld — and the scalars.  Each value is formed by lane_sweeps' expression from operands of the same bits.
+template <int C>
+__device__ __forceinline__ void decade_lanes(const AssocParams &pr, const double *xent, int lane, EvalOut *evs, float *d1s, float *lls)
+{
+    constexpr int M = Shape<C>::M, G = 64 / M;
+    static_assert(C >= 1 && G >= 2, "decade_lanes: one covariate step at least, two lambdas per round at least");
+    const int tl = lane / M, k = lane - tl * M;
+    for (int t0 = 0; t0 < NLAM; t0 += G) {
+        const bool on = tl < G && t0 + tl < NLAM;     // lanes past the round's lambdas repeat its first one and write nothing
+        const int g = on ? tl : 0, t = t0 + g, base = g * M;
+        const double2 *tab = reinterpret_cast<const double2 *>(pr.dtab + (size_t)t * assoc_dtab_doubles(C));
+        double P = xent[t * 2 * M + k], Q = xent[t * 2 * M + M + k];
+#pragma unroll
+        for (int q = 0; q < C; q++) {
+            const double2 s = tab[(q * M + k) * 2], w = tab[(q * M + k) * 2 + 1];
+            const double ia = s.x, ba2 = s.y;
+            const double xp = __shfl(P, base + q, 64), xq = __shfl(Q, base + q, 64);
+            const double ur = (k == C + 1) ? w.x : xp, uc = (k < C) ? w.x : xp;
+            const double vr = (k == C + 1) ? w.y : xq, vc = (k < C) ? w.y : xq;
+            double s1 = fma(ba2 * uc, ur, Q);
+            double s2 = fma(ia * uc, vr, 0.0); s2 = fma(ia * vc, ur, s2);
+            double qn = s1 + s2;
+            double pn = fma(ia * uc, ur, P);
+            if (q == C - 1 && k == C) { qn = dmaxf(qn, PG_MINV); pn = dmaxf(pn, PG_MINV); }
+            if (k > q) { Q = qn; P = pn; }
+        }
+        // the pivot on x: only (y, y) is left to update
+        const double a = __shfl(P, base + C, 64), b = __shfl(Q, base + C, 64);
+        const double u = __shfl(P, base + C + 1, 64), v = __shfl(Q, base + C + 1, 64);
+        const double2 z0 = tab[C * M * 2], z1 = tab[C * M * 2 + 1], z2 = tab[C * M * 2 + 2], z3 = tab[C * M * 2 + 3];
+        const double t1 = z2.x;
+        const float ldH = (float)z2.y, lam = (float)z3.x;
+        EvalOut e;
+        e.Pxx_c = (float)a; e.Pyx_c = (float)u;
+        const double a2 = a * a, ia = -1.0 / a, ba2 = b / a2;
+        const double trP = z0.x - b / a;
+        double s1 = fma(ba2 * u, u, z1.y);
+        double s2 = fma(ia * u, v, 0.0); s2 = fma(ia * v, u, s2);
+        const double qn = dmaxf(s1 + s2, PG_MINV);
+        const double pn = dmaxf(fma(ia * u, u, z1.x), PG_MINV);
+        e.yPy = (float)pn; e.yPPy = (float)qn; e.yPPPy = 0.0f;
+        e.trP = (float)trP; e.trPP = 0.0f;
+        e.ld = (float)((double)(float)z0.y + log(a));
+        e.sh = (float)t1; e.shh = 0.0f;
+        if (on && k == 0) {
+            evs[t] = e;
+            d1s[t] = d1_f(pr, lam, e.yPy, e.yPPy, e.trP);
+            lls[t] = logl_f(pr, e.yPy, ldH, e.ld);
+        }
+    }
+}
+
 template <int C, bool LRT, bool PHENO = false>
 // PHENO (pg_assoc_pheno_dev; never with LRT): the decade scan's x-entries are read from pr.xbuf; one launch per phenotype, so that
 // every (SNP, phenotype) is one wavefront and a workgroup holds WPB of them, as in a single-phenotype launch.
 // two waves per SIMD for EVERY c (PG_WAVES = 2): a lone wave cannot issue fp64 VALU at the pipe's rate (measured 2.3x faster at 2 than at
-// 1).  From c = 4 on the instantiations are capped at 256 VGPRs with spills to scratch (c = 5: 81 VGPR + 40 SGPR spills, 208 B; c = 10:
-// 121, 356 B; c = 14: 572 B) — all of them in the per-evaluation outer loops; the Gram loops themselves are scratch-free (checked on the
+// 1).  From c = 4 on the instantiations are capped at 256 VGPRs with spills to scratch (c = 5: 76 VGPR + 38 SGPR spills, 228 B; c = 10:
+// 120, 352 B; c = 14: 564 B) — all of them in the per-evaluation outer loops; the Gram loops themselves are scratch-free (checked on the
 // shipped code object: VERDICT r3)
 __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams pr)
 {
@@ -982,6 +1095,7 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
     static_assert(!(PHENO && LRT), "the multi-phenotype search has no LRT");
     const long long g = (long long)blockIdx.x * WPB + wave;
     if (g >= pr.p) return;  // whole wavefront leaves; no workgroup barrier is used anywhere in this kernel
+    ASSOC_STAMP(0);
     // per-wave LDS: [piv] | [sav] | xent[NLAM][2M] doubles | evs[NLAM] | d1s[NLAM] | lls[NLAM] | vals[n_vals]
     constexpr size_t piv_bytes = Shape<C>::SWEEP_LDS ? (size_t)3 * M * 8 : 0;
     constexpr bool REUSE = Shape<C>::NEWTON_REUSE;
@@ -1010,7 +1124,12 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
         scan_all<C, 0>(pr, xrow, lane, xent);
     }
     wave_lds_sync();
-    for (int t = 0; t < NLAM; t++) {
+    ASSOC_STAMP(1);
+    // the decade sweeps: lane-parallel on the decade table, or — the multi-phenotype search, c = 0, rows too wide for two lambdas
+    // per round — every lambda's whole sweep in turn
+    constexpr bool HOIST = PG_ASSOC_DECADE_HOIST && !PHENO && C >= 1 && 64 / M >= 2;
+    if constexpr (HOIST) decade_lanes<C>(pr, xent, lane, evs, d1s, lls);
+    else for (int t = 0; t < NLAM; t++) {
         double P[SLOTS], Q[SLOTS], R[SLOTS];
         const double *fp = pr.fixg + ((size_t)t * 2 + 0) * NP, *fq = pr.fixg + ((size_t)t * 2 + 1) * NP;
         const double *xe = xent + t * 2 * M;
@@ -1031,6 +1150,7 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
             lls[t] = logl_f(pr, e.yPy, pr.ldHtab[t], e.ld);
         }
     }
+    ASSOC_STAMP(2);
     wave_lds_sync();
     // ---- candidate selection (pyx:109-117 / :144-152): start from the two boundaries
     float best_l = lls[0], best_lambda;
@@ -1178,6 +1298,7 @@ __global__ __launch_bounds__(64 * WPB, PG_WAVES) void assoc_kernel(AssocParams p
             atomicAdd(&pr.passes[2], (unsigned long long)n_full); atomicAdd(&pr.passes[3], (unsigned long long)n_reuse);
         }
     }
+    ASSOC_STAMP(3);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1932,7 +2053,8 @@ static int assoc_run(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, c
     const size_t off_fixg = ((size_t)NLAM * pr.npad * 4 + 255) & ~(size_t)255;
     const size_t off_t1 = off_fixg + (size_t)NLAM * 2 * NP * 8;
     const size_t off_ldh = off_t1 + NLAM * 8;
-    rc = ensure(ctx, &ctx->tabs, &ctx->tabs_bytes, off_ldh + NLAM * 4 + 256);
+    const size_t off_dtab = (off_ldh + NLAM * 4 + 255) & ~(size_t)255;
+    rc = ensure(ctx, &ctx->tabs, &ctx->tabs_bytes, off_dtab + NLAM * assoc_dtab_doubles(c) * 8 + 256);
     if (rc) return rc;
     if (!ctx->stats) PG_HIP(hipMalloc(&ctx->stats, 16));
     pr.fixed = (const float *)ctx->fixed;
@@ -1940,6 +2062,7 @@ static int assoc_run(pg_ctx *ctx, int64_t n, int c, int64_t p, const float *d, c
     pr.fixg = (double *)((char *)ctx->tabs + off_fixg);
     pr.t1tab = (double *)((char *)ctx->tabs + off_t1);
     pr.ldHtab = (float *)((char *)ctx->tabs + off_ldh);
+    pr.dtab = (double *)((char *)ctx->tabs + off_dtab);
     pr.lrt = lrt ? 1 : 0;
     pr.lalt = lalt; pr.lamalt = lamalt;
     pr.beta = beta; pr.se = se; pr.tau = tau; pr.lam = lambda; pr.F = F;
@@ -1987,7 +2110,8 @@ extern "C" int pg_assoc_warm(pg_ctx *ctx, int64_t n, int c)
     rc = ensure(ctx, &ctx->fixed, &ctx->fixed_bytes, (size_t)npad * rowf * 4);
     if (rc) return rc;
     const size_t off_fixg = ((size_t)NLAM * npad * 4 + 255) & ~(size_t)255;
-    rc = ensure(ctx, &ctx->tabs, &ctx->tabs_bytes, off_fixg + (size_t)NLAM * 2 * NP * 8 + NLAM * 8 + NLAM * 4 + 256);
+    rc = ensure(ctx, &ctx->tabs, &ctx->tabs_bytes,
+                ((off_fixg + (size_t)NLAM * 2 * NP * 8 + NLAM * 8 + NLAM * 4 + 255) & ~(size_t)255) + NLAM * assoc_dtab_doubles(c) * 8 + 256);
     if (rc) return rc;
     if (!ctx->stats) PG_HIP(hipMalloc(&ctx->stats, 16));
     return PG_OK;
@@ -2012,6 +2136,13 @@ extern "C" int pg_assoc_set_pass_stats(pg_ctx *ctx, unsigned long long *dev4)
     ctx->pass_stats = dev4;
     return PG_OK;
 }
+
+#ifdef PG_ASSOC_STAMPS
+extern "C" int pgx_assoc_stamps(long long *out4096)    // [1024 SNPs][entry, decade sweeps begin, end, exit] of the last pg_assoc_dev launch
+{
+    return hipMemcpyFromSymbol(out4096, HIP_SYMBOL(pg::g_assoc_stamps), sizeof(long long) * 4096) == hipSuccess ? 0 : -1;
+}
+#endif
 
 // ---- several phenotypes over one SNP block: pg_assoc_dev's results for each, with the decade scan's y-free entries shared ----------
 // Scratch of one call, in ctx->pheno: the fixed rows and fixg tables of a chunk of PHENO_CHUNK phenotypes, the phenotype-free tables
