@@ -279,6 +279,23 @@ int pg_ld_block_dev(pg_ctx *ctx, int64_t n, const void *A, int64_t pea, int64_t 
 int pg_ld_band_dev(pg_ctx *ctx, int64_t n, const void *image, int64_t pe, int64_t j0, int64_t rows, int64_t have, int64_t w, float *band,
                    int64_t ldo, int *sums);
 
+/* ---- LD scores (csrc/ld.hip): l_j = sum over a window of r^2(j, k), the regressor of LD score regression, from the
+ * pairs of pg_ld_band_dev without their band.  Image, rows, have and w as there, with a width per row:
+ *   pairs   : rows j in [j0, j0 + rows) against j + 1 + k, 0 <= k < min(w, reach[j]) (reach NULL: w for every row); a partner at or
+ *             past `have` is skipped.  reach, sum, npairs and nobs are indexed by image position (a stream passes ptr + base).
+ *   value   : with the pair's exact int64 ca, cb, cab (above) the pair is DEFINED when ca > 0 and cb > 0 and, with adjust != 0, N > 2;
+ *             then in fp64, every operation rounded once,  r2 = min(((double)cab (double)cab) / ((double)ca (double)cb), 1),  with adjust
+ *             r2 = r2 - (1 - r2) / (double)(N - 2)  (the ldsc bias correction with the pair's own N),  q = rint(r2 2^32) to nearest even.
+ *   sum, npairs : a defined pair ADDS q to sum[j] and to sum[partner] and 1 to npairs[j] and to npairs[partner]; an undefined pair adds
+ *             nothing.  Accumulated in integer atomics (the caller zeroes them once): the same bits in any order, whatever the batch
+ *             boundaries, the tile order or PG_LD_PLANES.  l_j = 1 + sum[j] / 2^32.
+ *   nobs    : WRITTEN for the rows: n - missing calls when the SNP's own variance term (n - miss) sum x^2 - (sum x)^2 is positive, else 0
+ *             (monomorphic, all missing, not hard-call).  Nothing else of nobs is touched.
+ * PG_EINVAL for what pg_ld_band_dev refuses, a NULL sum, npairs or nobs, w >= 2^28 (2 w 2^32 stays inside int64) and a sum off 8 bytes:
+ * a refused call enqueues nothing. */
+int pg_ld_score_dev(pg_ctx *ctx, int64_t n, const void *image, int64_t pe, int64_t j0, int64_t rows, int64_t have, int64_t w,
+                    const int32_t *reach, int adjust, int64_t *sum, int32_t *npairs, int32_t *nobs);
+
 /* ---- Polygenic scores from RAW genotypes on the fp64 matrix pipe (csrc/prs.hip): S = G W, PLINK's --score, accumulated over
  * the SNP batches of a stream.  Block conventions of pg_snp_stats_x_dev / pg_snp_stats_bed_dev: an (n x pb) sample-major (snp_major = 0,
  * ldX >= pb) or (pb x n) SNP-major (ldX >= n) block of dtype PG_DTYPE_*, or pb packed .bed records (ldb >= ceil(n/4) bytes; code

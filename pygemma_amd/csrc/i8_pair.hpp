@@ -124,13 +124,13 @@ __device__ __forceinline__ void i8p_stage(const I8pLane g, int half, const intx4
     __syncthreads();
 }
 
-// raises Kernel's dynamic-LDS limit to I8P_LDS, once per device
-template <auto Kernel> static hipError_t i8p_lds_limit(int device)
+// raises Kernel's dynamic-LDS limit to I8P_LDS (or to Bytes, for a kernel that keeps something of its own behind the tile), once per device
+template <auto Kernel, int Bytes = I8P_LDS> static hipError_t i8p_lds_limit(int device)
 {
     static std::atomic<unsigned long long> done{0};
     const unsigned long long bit = 1ULL << (device & 63);
     if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, I8P_LDS);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Bytes);
     if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
     return e;
 }

@@ -20,7 +20,8 @@
 // the 3 x 3 plane products (three of them are waste).  Nine GEMM tiles instead of one for the same pairs; both paths produce the same integers.
 // PG_LD_PLANES=1 sends every tile pair down the three-plane path (tests, A/B timing).
 // Two output mappings: a dense block r[ia][ib], and a band, band[j][k] = r(j, j + 1 + k), for which only the tile pairs (and, inside the
-// three-plane path, the sub-tile pairs) that meet the band are launched or run.
+// three-plane path, the sub-tile pairs) that meet the band are launched or run.  A third epilogue keeps nothing per pair: the band's pairs,
+// each within a reach of its row, as r^2 in fixed point summed per SNP (LD scores, pg_ld_score_dev).
 #include "geno_src.hpp"
 #include "i8_pair.hpp"
 
@@ -35,6 +36,7 @@ constexpr int LD_T3 = 84;         // SNPs per sub-tile side, three-plane path: 2
 constexpr int LD_H3 = 42;
 constexpr long long LD_MAXN = 1LL << 28;      // exclusive: every sum fits int32 (4 n < 2^31), every product int64
 constexpr long long LD_MAXPE = 1LL << 31;
+constexpr long long LD_SCORE_MAXW = 1LL << 28;      // exclusive: a SNP's 2 w pairs of at most 2^32 each stay inside int64
 
 struct LdLayout {
     long long ldk;
@@ -179,6 +181,11 @@ struct LdPair {
     float *r;
     long long ldr;
     int *sums;
+    // the score epilogue (band pairs only): every pair within min(w, reach[row]) credits both of its SNPs
+    const int *reach;
+    int adjust;
+    long long *sum;
+    int *npairs, *nobs;
 };
 
 // r and the six sums of one pair, to their place (o: element index of the pair in the output)
@@ -201,7 +208,101 @@ __device__ __forceinline__ void ld_store(const LdPair &q, long long o, bool vali
     }
 }
 
-__global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
+// ---- the score epilogue: a pair's r^2 in fixed point at 2^-32, summed per SNP in integers ---------------------------------
+// the accumulators of a (sub-)tile pair, behind the pair tile's LDS: 256 int64 sums and 256 int32 counts of the columns (the B
+// SNPs), then the same of the rows (the A SNPs)
+constexpr int LD_SCORE_LDS = I8P_LDS + 2 * 256 * 12;
+__device__ __forceinline__ unsigned long long *ld_acc_sum(int side) { return reinterpret_cast<unsigned long long *>(i8p_lds + I8P_LDS + side * 256 * 12); }
+__device__ __forceinline__ int *ld_acc_cnt(int side) { return reinterpret_cast<int *>(i8p_lds + I8P_LDS + side * 256 * 12 + 256 * 8); }
+
+// q = rint(2^32 r^2) of a pair, r^2 = min(cab^2 / (ca cb), 1) less the ldsc bias (1 - r^2) / (N - 2) when `adjust`: three (five)
+// correctly rounded fp64 operations on exact integers, so a host model gets the same bits.  false: the pair is undefined.
+__device__ __forceinline__ bool ld_r2_fixed(int adjust, long long N, long long Sa, long long Sb, long long Saa, long long Sbb, long long Sab,
+                                            long long &qv)
+{
+    const long long ca = N * Saa - Sa * Sa, cb = N * Sbb - Sb * Sb, cab = N * Sab - Sa * Sb;
+    if (ca <= 0 || cb <= 0 || (adjust && N <= 2)) return false;
+    double r2 = ((double)cab * (double)cab) / ((double)ca * (double)cb);
+    r2 = r2 > 1.0 ? 1.0 : r2;
+    if (adjust) r2 = r2 - (1.0 - r2) / (double)(N - 2);
+    qv = __double2ll_rn(r2 * 4294967296.0);
+    return true;
+}
+
+// One staged half.  LW lanes walk a row, lane + LW c its columns: 64 for the 252-SNP tile, 32 (two rows to a wavefront) for the 84-SNP
+// sub-tile, whose rows would leave 44 of 128 column slots idle.  A row belongs to one wavefront in one half: its sum meets in a
+// reduction over the LW lanes and is stored to the row accumulator; the column sums meet in the column accumulators, where the lanes
+// of a row add to LW different words.
+template <int LW> __device__ __forceinline__ void ld_score_half(const LdPair &q, const I8pLane ln, int half, int T, long long as0, long long as1,
+                                                                long long bs0, long long bs1, long long bend)
+{
+    constexpr bool three = LW == 32;
+    constexpr int RW = 64 / LW, ha = three ? LD_H3 : 128;
+    const int *const stg = i8p_staged();
+    const int lr = ln.lane / LW, lc = ln.lane % LW;
+#pragma unroll 1
+    for (int sa0 = ln.wave * RW; sa0 < ha; sa0 += 8 * RW) {
+        const int sa = sa0 + lr;
+        const long long ja = as0 + half * ha + sa;
+        bool row = sa < ha && ja < as1;
+        long long lim = 0;                                          // partners ja + 1 .. ja + lim
+        if (row) lim = q.reach ? min(q.w, (long long)q.reach[ja]) : q.w;
+        row = row && lim > 0 && bs0 <= ja + lim && bs0 + T > ja + 1;
+        if (!__any(row)) continue;
+        int4 a = make_int4(0, 0, 0, 0);
+        if (!three && row) a = q.ta[ja];
+        long long rs = 0;
+        int rc = 0;
+#pragma unroll 1
+        for (int sb = lc; sb < T; sb += LW) {
+            const long long jb = bs0 + sb, k = jb - ja - 1;
+            if (!row || jb >= bs1 || jb >= bend || k < 0 || k >= lim) continue;      // bend: q.w is clamped to `have` for the first row only
+            long long N, Sa, Sb, Saa, Sbb, Sab, qv;
+            if (three) {
+                const int *s = stg + sa * I8P_LDW + (sb / LD_H3) * 128 + sb % LD_H3;      // [plane of a][plane of b] at (pa 42) rows, (pb 42) columns
+                Sab = s[0];                        Sb = s[LD_H3 * I8P_LDW];                 Sa = s[LD_H3];
+                N = s[LD_H3 * I8P_LDW + LD_H3];     Saa = s[2 * LD_H3 * I8P_LDW + LD_H3];    Sbb = s[LD_H3 * I8P_LDW + 2 * LD_H3];
+            } else {
+                const int4 b = q.tb[jb];
+                N = q.n; Sa = a.x; Saa = a.y; Sb = b.x; Sbb = b.y;
+                Sab = stg[sa * I8P_LDW + sb];
+            }
+            if (ld_r2_fixed(q.adjust, N, Sa, Sb, Saa, Sbb, Sab, qv)) {
+                rs += qv; rc += 1;
+                atomicAdd(ld_acc_sum(0) + sb, (unsigned long long)qv);
+                atomicAdd(ld_acc_cnt(0) + sb, 1);
+            }
+        }
+        for (int k = 1; k < LW; k <<= 1) {
+            rs += __shfl_xor(rs, k, 64); rc += __shfl_xor(rc, k, 64);
+        }
+        if (lc == 0 && rc) {
+            ld_acc_sum(1)[half * ha + sa] = (unsigned long long)rs;
+            ld_acc_cnt(1)[half * ha + sa] = rc;
+        }
+    }
+}
+
+// The accumulators of a finished (sub-)tile pair (the last half's barrier is behind us) go out: threads [0, 256) the columns from bs0,
+// threads [256, 512) the rows from as0, one 64-bit and one 32-bit atomic per SNP with a defined pair, 64 neighbouring SNPs to a
+// wavefront; and zeros for the next pair, whose first add lies behind the barriers of its products.
+__device__ __forceinline__ void ld_score_out(const LdPair &q, long long as0, long long bs0)
+{
+    const int side = threadIdx.x >> 8, t = threadIdx.x & 255;
+    const unsigned long long s = ld_acc_sum(side)[t];
+    const int c = ld_acc_cnt(side)[t];
+    if (c) {      // a defined pair: the SNP is one with data
+        const long long g = (side ? as0 : bs0) + t;
+        atomicAdd(reinterpret_cast<unsigned long long *>(q.sum + g), s);
+        atomicAdd(q.npairs + g, c);
+        ld_acc_sum(side)[t] = 0;
+        ld_acc_cnt(side)[t] = 0;
+    }
+}
+
+// SCORE = false: r (and the six sums) of every pair to a block or a band.  SCORE = true: the band's pairs, each within its row's reach,
+// reduced to the fixed-point sum of r^2 and the pair count of both of its SNPs; the rows' called-sample counts to nobs.
+template <bool SCORE> __global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
 {
     const int tid = threadIdx.x;
     const I8pLane ln = i8p_lane();
@@ -218,6 +319,19 @@ __global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
     const bool three = __syncthreads_or(miss) != 0;
     const int T = three ? LD_T3 : LD_T1, nsub = three ? 3 : 1;
     const int *const stg = i8p_staged();
+    if constexpr (SCORE) {
+        ld_acc_sum(tid >> 8)[tid & 255] = 0;      // ordered before the first add by the barriers of the first products
+        ld_acc_cnt(tid >> 8)[tid & 255] = 0;
+        // the rows' own called samples, once per A tile: n - missing calls where the SNP's own variance term is positive
+        if (tile_b == tile_a)
+            for (int k = tid; k < LD_T1; k += 512) {
+                const long long g = abase + k;
+                if (g >= aend) continue;
+                const int4 t = q.ta[g];
+                const long long nm = (long long)q.n - t.z;
+                q.nobs[g] = nm * t.y - (long long)t.x * t.x > 0 ? (int)nm : 0;
+            }
+    }
 
 #pragma unroll 1
     for (int sub = 0; sub < nsub * nsub; sub++) {
@@ -228,6 +342,8 @@ __global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
         const long long bs1 = q.band ? min(bs0 + T, as1 + q.w) : min(bs0 + T, bend);
         if (bs0 >= bs1 || (q.band && bs0 + T <= as0 + 1)) continue;
         const bool data = bs0 < bend;                                                        // band: partners at or past `have` are NaN
+        if constexpr (SCORE)
+            if (!data) continue;                                                             // ... and credit nobody
         intx4 acc[4][8];
         i8p_zero(acc);
         if (data) {
@@ -249,45 +365,57 @@ __global__ __launch_bounds__(512, 1) void ld_pair_kernel(LdPair q)
             i8p_products(ln, srcA, srcB, q.KT, acc);
         }
         // ---- epilogue: the accumulators meet through LDS, one 128-row half of A at a time
+        if constexpr (SCORE) {
 #pragma unroll 1
-        for (int half = 0; half < 2; half++) {
-            i8p_stage(ln, half, acc);
-            const int ha = three ? LD_H3 : 128;                   // A SNPs in this half
-            for (int idx = tid; idx < ha * T; idx += 512) {
-                const int sa = idx / T, sb = idx - sa * T;
-                const long long ja = as0 + half * ha + sa, jb = bs0 + sb;
-                if (ja >= as1 || jb >= bs1 || half * ha + sa >= T) continue;
-                long long o;
-                if (q.band) {
-                    const long long k = jb - ja - 1;
-                    if (k < 0 || k >= q.w) continue;
-                    o = (ja - q.a0) * q.ldr + k;
-                } else o = (ja - q.a0) * q.ldr + (jb - q.b0);
-                const bool valid = jb < bend;
-                long long N = 0, Sa = 0, Sb = 0, Saa = 0, Sbb = 0, Sab = 0;
-                if (valid && three) {
-                    const int *s = stg + sa * I8P_LDW + (sb / LD_H3) * 128 + sb % LD_H3;      // [plane of a][plane of b] at (pa 42) rows, (pb 42) columns
-                    Sab = s[0];                        Sb = s[LD_H3 * I8P_LDW];                 Sa = s[LD_H3];
-                    N = s[LD_H3 * I8P_LDW + LD_H3];     Saa = s[2 * LD_H3 * I8P_LDW + LD_H3];    Sbb = s[LD_H3 * I8P_LDW + 2 * LD_H3];
-                } else if (valid) {
-                    const int4 a = q.ta[ja], b = q.tb[jb];
-                    N = q.n; Sa = a.x; Saa = a.y; Sb = b.x; Sbb = b.y;
-                    Sab = stg[sa * I8P_LDW + sb];
-                }
-                ld_store(q, o, valid, N, Sa, Sb, Saa, Sbb, Sab);
+            for (int half = 0; half < 2; half++) {
+                i8p_stage(ln, half, acc);
+                if (three) ld_score_half<32>(q, ln, half, T, as0, as1, bs0, bs1, bend);
+                else ld_score_half<64>(q, ln, half, T, as0, as1, bs0, bs1, bend);
+                __syncthreads();
             }
-            __syncthreads();
+            ld_score_out(q, as0, bs0);
+        } else {
+#pragma unroll 1
+            for (int half = 0; half < 2; half++) {
+                i8p_stage(ln, half, acc);
+                const int ha = three ? LD_H3 : 128;                   // A SNPs in this half
+                for (int idx = tid; idx < ha * T; idx += 512) {
+                    const int sa = idx / T, sb = idx - sa * T;
+                    const long long ja = as0 + half * ha + sa, jb = bs0 + sb;
+                    if (ja >= as1 || jb >= bs1 || half * ha + sa >= T) continue;
+                    long long o;
+                    if (q.band) {
+                        const long long k = jb - ja - 1;
+                        if (k < 0 || k >= q.w) continue;
+                        o = (ja - q.a0) * q.ldr + k;
+                    } else o = (ja - q.a0) * q.ldr + (jb - q.b0);
+                    const bool valid = jb < bend;
+                    long long N = 0, Sa = 0, Sb = 0, Saa = 0, Sbb = 0, Sab = 0;
+                    if (valid && three) {
+                        const int *s = stg + sa * I8P_LDW + (sb / LD_H3) * 128 + sb % LD_H3;      // [plane of a][plane of b] at (pa 42) rows, (pb 42) columns
+                        Sab = s[0];                        Sb = s[LD_H3 * I8P_LDW];                 Sa = s[LD_H3];
+                        N = s[LD_H3 * I8P_LDW + LD_H3];     Saa = s[2 * LD_H3 * I8P_LDW + LD_H3];    Sbb = s[LD_H3 * I8P_LDW + 2 * LD_H3];
+                    } else if (valid) {
+                        const int4 a = q.ta[ja], b = q.tb[jb];
+                        N = q.n; Sa = a.x; Saa = a.y; Sb = b.x; Sbb = b.y;
+                        Sab = stg[sa * I8P_LDW + sb];
+                    }
+                    ld_store(q, o, valid, N, Sa, Sb, Saa, Sbb, Sab);
+                }
+                __syncthreads();
+            }
         }
     }
 }
 
-static int launch_ld_pair(pg_ctx *ctx, LdPair q, long long tiles_a, long long tiles_b, const char *who)
+template <bool SCORE> static int launch_ld_pair(pg_ctx *ctx, LdPair q, long long tiles_a, long long tiles_b, const char *who)
 {
     PG_REQUIRE(tiles_a * tiles_b < (1LL << 31), "%s: too many tiles (%lld x %lld)", who, tiles_a, tiles_b);
     q.tiles_b = (int)tiles_b;
     q.planes = env_flag("PG_LD_PLANES");
-    PG_HIP(i8p_lds_limit<ld_pair_kernel>(ctx->device));
-    ld_pair_kernel<<<(unsigned)(tiles_a * tiles_b), 512, I8P_LDS, ctx->stream>>>(q);
+    constexpr int lds = SCORE ? LD_SCORE_LDS : I8P_LDS;
+    PG_HIP((i8p_lds_limit<ld_pair_kernel<SCORE>, lds>(ctx->device)));
+    ld_pair_kernel<SCORE><<<(unsigned)(tiles_a * tiles_b), 512, lds, ctx->stream>>>(q);
     PG_HIP(hipGetLastError());
     return PG_OK;
 }
@@ -386,7 +514,8 @@ extern "C" int pg_ld_block_dev(pg_ctx *ctx, int64_t n, const void *A, int64_t pe
     q.A = static_cast<const signed char *>(A); q.pea = pea; q.ta = reinterpret_cast<const int4 *>(static_cast<const char *>(A) + La.totals);
     q.B = static_cast<const signed char *>(B); q.peb = peb; q.tb = reinterpret_cast<const int4 *>(static_cast<const char *>(B) + Lb.totals);
     q.a0 = a0; q.na = na; q.b0 = b0; q.nb = nb; q.r = r; q.ldr = ldr; q.sums = sums;
-    return launch_ld_pair(ctx, q, (na + LD_T1 - 1) / LD_T1, (nb + LD_T1 - 1) / LD_T1, "pg_ld_block_dev");
+    q.reach = nullptr; q.adjust = 0; q.sum = nullptr; q.npairs = q.nobs = nullptr;
+    return launch_ld_pair<false>(ctx, q, (na + LD_T1 - 1) / LD_T1, (nb + LD_T1 - 1) / LD_T1, "pg_ld_block_dev");
 }
 
 extern "C" int pg_ld_band_dev(pg_ctx *ctx, int64_t n, const void *image, int64_t pe, int64_t j0, int64_t rows, int64_t have, int64_t w, float *band,
@@ -405,6 +534,29 @@ extern "C" int pg_ld_band_dev(pg_ctx *ctx, int64_t n, const void *image, int64_t
     q.A = q.B = static_cast<const signed char *>(image); q.pea = q.peb = pe;
     q.ta = q.tb = reinterpret_cast<const int4 *>(static_cast<const char *>(image) + L.totals);
     q.a0 = q.b0 = j0; q.na = rows; q.nb = have - j0; q.r = band; q.ldr = ldo; q.sums = sums;
+    q.reach = nullptr; q.adjust = 0; q.sum = nullptr; q.npairs = q.nobs = nullptr;
     // the partners of A tile t, SNPs (252 t, 252 t + 251 + w], lie in the B tiles t .. t + (251 + w) / 252
-    return launch_ld_pair(ctx, q, (rows + LD_T1 - 1) / LD_T1, 1 + (LD_T1 - 1 + w) / LD_T1, "pg_ld_band_dev");
+    return launch_ld_pair<false>(ctx, q, (rows + LD_T1 - 1) / LD_T1, 1 + (LD_T1 - 1 + w) / LD_T1, "pg_ld_band_dev");
+}
+
+extern "C" int pg_ld_score_dev(pg_ctx *ctx, int64_t n, const void *image, int64_t pe, int64_t j0, int64_t rows, int64_t have, int64_t w,
+                               const int32_t *reach, int adjust, int64_t *sum, int32_t *npairs, int32_t *nobs)
+{
+    PG_REQUIRE(ctx && image && sum && npairs && nobs, "pg_ld_score_dev: NULL argument");
+    PG_REQUIRE(ld_aligned(image), "pg_ld_score_dev: the image must lie on 16 bytes");
+    PG_REQUIRE((uintptr_t)sum % 8 == 0, "pg_ld_score_dev: sum must lie on 8 bytes");
+    PG_REQUIRE(ld_shape_ok(n, pe) && j0 >= 0 && rows >= 0 && j0 + rows <= have && have <= pe && w >= 1 && w < LD_SCORE_MAXW,
+               "pg_ld_score_dev: bad shape n=%lld rows [%lld, +%lld), have=%lld of %lld, w=%lld", (long long)n, (long long)j0, (long long)rows,
+               (long long)have, (long long)pe, (long long)w);
+    if (rows == 0) return PG_OK;
+    PG_HIP(hipSetDevice(ctx->device));
+    const LdLayout L = ld_layout(n, pe);
+    LdPair q;
+    q.n = (int)n; q.ldk = L.ldk; q.KT = (int)(L.ldk / LD_BK); q.band = 1;
+    q.w = w < have - 1 - j0 ? w : have - 1 - j0;      // no partner at or past `have`: the B tiles beyond it are not launched
+    q.A = q.B = static_cast<const signed char *>(image); q.pea = q.peb = pe;
+    q.ta = q.tb = reinterpret_cast<const int4 *>(static_cast<const char *>(image) + L.totals);
+    q.a0 = q.b0 = j0; q.na = rows; q.nb = have - j0; q.r = nullptr; q.ldr = 0; q.sums = nullptr;
+    q.reach = reach; q.adjust = adjust != 0; q.sum = reinterpret_cast<long long *>(sum); q.npairs = npairs; q.nobs = nobs;
+    return launch_ld_pair<true>(ctx, q, (rows + LD_T1 - 1) / LD_T1, 1 + (LD_T1 - 1 + q.w) / LD_T1, "pg_ld_score_dev");
 }

@@ -41,8 +41,8 @@ from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_re
 from . import model as _model
 
 __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
-           "kinship", "ld", "ld_window", "ld_prune", "clump", "prs", "prs_weights", "king", "ibs", "sample_stats", "related_pairs",
-           "unrelated", "pca", "pca_project", "PcaResult"] + _model.__all__
+           "kinship", "ld", "ld_window", "ld_prune", "clump", "ld_scores", "ldsc", "LdscResult", "prs", "prs_weights", "king", "ibs",
+           "sample_stats", "related_pairs", "unrelated", "pca", "pca_project", "PcaResult"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
@@ -1001,11 +1001,51 @@ def _signed(coord):
     return coord.astype(np.int64 if coord.dtype.kind in "iub" else np.float64)
 
 
+def _check_span(window, pos):
+    """A window in columns is a positive integer; one in the units of `pos` any number of at least 1."""
+    if pos is None:
+        _check_window(window)
+    elif not (isinstance(window, (int, float, np.integer, np.floating)) and window >= 1):
+        raise ValueError(f"window must be at least 1, not {window!r}")
+
+
+def _coords(p, chrom, pos):
+    """(coord, run) of p SNPs: the coordinate a window is measured in (`pos`, checked; the column without it) and the number of the
+    chromosome run a SNP lies in (a window never crosses a change of `chrom`)."""
+    run = np.zeros(p, np.int64)
+    if chrom is not None:
+        chrom = np.asarray(chrom)
+        if chrom.shape != (p,):
+            raise ValueError(f"shape mismatch: chrom has shape {chrom.shape} for {p} SNPs")
+        run[1:] = np.cumsum(chrom[1:] != chrom[:-1])
+    coord = np.arange(p, dtype=np.int64)
+    if pos is not None:
+        coord = np.asarray(pos)
+        if coord.shape != (p,) or coord.dtype.kind not in "iuf":
+            raise ValueError(f"shape mismatch: pos must be {p} numbers, got shape {coord.shape} of {coord.dtype}")
+        if coord.dtype.kind == "u" and coord.size and coord.max() > np.iinfo(np.int64).max:
+            raise ValueError("pos does not fit int64")
+        coord = _signed(coord)
+        if ((np.diff(coord) < 0) & (run[1:] == run[:-1])).any() or not np.isfinite(coord).all():
+            raise ValueError("pos must be finite and nondecreasing within a chromosome")
+    return coord, run
+
+
 def _clump_reach(coord, run, window):
-    """Two pointers over candidates in column order: for candidate c the number of later candidates of its chromosome run within
-    `window` of it; the largest is the band width clumping needs."""
-    coord, m = _signed(coord), len(coord)
+    """For candidate c, in column order, the number of later candidates of its chromosome run within `window` of it; the largest is
+    the band width clumping (or an LD score) needs.  Integer coordinates (columns, base pairs; nondecreasing within a run, as the
+    callers check) are bisected run by run; any other (centimorgans) walk two pointers in a Python loop, O(p) interpreted steps."""
+    coord, run, m = _signed(coord), np.asarray(run), len(coord)
     reach = np.zeros(m, np.int64)
+    if coord.dtype.kind == "i" and m:
+        top = np.iinfo(np.int64).max
+        span = int(min(np.floor(window), top))
+        starts = np.flatnonzero(np.concatenate([[True], run[1:] != run[:-1]]))
+        for s, e in zip(starts, np.concatenate([starts[1:], [m]])):
+            seg = coord[s:e]
+            last = seg + np.minimum(span, top - np.maximum(seg, 0))      # the furthest coordinate in reach, without wrapping int64
+            reach[s:e] = np.searchsorted(seg, last, side="right") - 1 - np.arange(e - s)
+        return reach
     hi = 0
     for c in range(m):
         hi = max(hi, c)
@@ -1052,10 +1092,7 @@ def clump(df, X, p1=1e-4, p2=1e-2, r2=0.5, window=250, col="p_wald", chrom=None,
     device work: what ld_window refuses, thresholds outside [0, 1], window < 1, `col` missing, lengths of df, chrom, pos that are not
     p, pos decreasing within a chromosome."""
     _check_unit(p1=p1, p2=p2, r2=r2)
-    if pos is None:
-        _check_window(window)
-    elif not (isinstance(window, (int, float, np.integer, np.floating)) and window >= 1):
-        raise ValueError(f"window must be at least 1, not {window!r}")
+    _check_span(window, pos)
     _check_snp_batch(stream_kw.get("snp_batch"))
     X = _ld_source(X, "clump")
     p = X.shape[1]
@@ -1064,22 +1101,7 @@ def clump(df, X, p1=1e-4, p2=1e-2, r2=0.5, window=250, col="p_wald", chrom=None,
     pv = np.asarray(df[col], np.float64)
     if pv.shape != (p,):
         raise ValueError(f"shape mismatch: {len(pv)} rows of p-values for {p} SNPs")
-    run = np.zeros(p, np.int64)
-    if chrom is not None:
-        chrom = np.asarray(chrom)
-        if chrom.shape != (p,):
-            raise ValueError(f"shape mismatch: chrom has shape {chrom.shape} for {p} SNPs")
-        run[1:] = np.cumsum(chrom[1:] != chrom[:-1])
-    coord = np.arange(p, dtype=np.int64)
-    if pos is not None:
-        coord = np.asarray(pos)
-        if coord.shape != (p,) or coord.dtype.kind not in "iuf":
-            raise ValueError(f"shape mismatch: pos must be {p} numbers, got shape {coord.shape} of {coord.dtype}")
-        if coord.dtype.kind == "u" and coord.size and coord.max() > np.iinfo(np.int64).max:
-            raise ValueError("pos does not fit int64")
-        coord = _signed(coord)
-        if ((np.diff(coord) < 0) & (run[1:] == run[:-1])).any() or not np.isfinite(coord).all():
-            raise ValueError("pos must be finite and nondecreasing within a chromosome")
+    coord, run = _coords(p, chrom, pos)
     with np.errstate(invalid="ignore"):
         cand = np.flatnonzero(pv < p2)
     width = int(_clump_reach(coord[cand], run[cand], window).max()) if cand.size else 0
@@ -1097,6 +1119,157 @@ def clump(df, X, p1=1e-4, p2=1e-2, r2=0.5, window=250, col="p_wald", chrom=None,
     res = pd.DataFrame(out, columns=list(out))
     res["members"] = pd.Series([cand[mem] for _, mem in clumps], dtype=object, index=res.index)
     return res
+
+
+# ---- LD scores and LD score regression (csrc/ld.hip) ----------------------------------------------------------------------
+_LDS_COLS = ("l2", "n_pairs", "n_obs", "reach_fwd")
+_LDS_MAX_W = 1 << 28     # pg_ld_score_dev: a SNP's 2 w pairs of at most 2^32 each stay inside int64
+_CHI2_1DF_MEDIAN = 0.454936423119572     # the median of a chi-square with one degree of freedom
+
+
+def ld_scores(X, window, *, pos=None, chrom=None, adjust=True, snps=None, snp_batch=None, device=0, verbose=0, stats=None):
+    """The LD score of every SNP of X, l2_j = 1 + sum of r^2(j, k) over the other SNPs k of its window: the regressor of LD score
+    regression (`ldsc`), which tells confounding (intercept) from polygenicity (slope) in an inflated lambda_GC.
+
+    X as for `ld_window`.  The window is `clump`'s: the partners of SNP j are the SNPs with |i - j| <= window in columns of X, or
+    |pos_i - pos_j| <= window when `pos` (length p, nondecreasing within a chromosome; base pairs or centimorgans) is given, and never
+    beyond a change of `chrom` (length p, the SNPs of one chromosome adjacent).  r is the pairwise-complete correlation `ld` defines; a
+    pair counts when both variances over its jointly called samples are positive and, with `adjust`, N > 2 of them are called.  In
+    fp64, r2 = min(cab^2 / (ca cb), 1), with `adjust` (the default, as ldsc estimates LD scores) less the bias (1 - r2) / (N - 2) with
+    the pair's own N, then rounded to fixed point at 2^-32 and summed in int64 on the device: the result is the same bits whatever the
+    batches, the storage of X or the order of the tiles.  The SNP's own r^2 = 1 is the leading 1, not adjusted.
+    Streamed like ld_window (one image of snp_batch + w SNPs, w the largest forward reach found on the host by _clump_reach), but every
+    tile's pairs are reduced in the kernel (pg_ld_score_dev): 16 bytes per SNP stay on the device until one download at the end, where
+    the band would be 4 w.  Returns a DataFrame of p rows:
+      l2         float64; NaN for a SNP without variance of its own (monomorphic, all missing, not hard-call: n_obs = 0)
+      n_pairs    int64, the pairs that counted, on both sides of the SNP
+      n_obs      int64, the SNP's called samples, 0 as above
+      reach_fwd  int64, the later SNPs inside the SNP's window
+      SNPs       `snps`, when given
+    `stats` receives batches, bytes_in, seconds and w.  Refused with ValueError before any device work: what ld_window and clump
+    refuse for these arguments (X, snp_batch, chrom, pos), `snps` of another length, a window that is not at least 1 or, without
+    `pos`, not an integer, a reach of 2^28 SNPs or more."""
+    _check_snp_batch(snp_batch)
+    _check_span(window, pos)
+    X = _ld_source(X, "ld_scores")
+    p = X.shape[1]
+    if snps is not None and len(snps) != p:
+        raise ValueError(f"shape mismatch: {len(snps)} SNP names for {p} SNPs")
+    coord, run = _coords(p, chrom, pos)
+    reach = _clump_reach(coord, run, window)
+    w = int(reach.max())
+    if w >= _LDS_MAX_W:
+        raise ValueError(f"a window of {w} SNPs is more than the int64 sums hold (2^28 at most)")
+    L, t0 = _lib.load(), time.time()
+    src = _describe(X)
+    n, wk = src.n, max(w, 1)          # w = 0 (one SNP, or every reach 0): the kernel still writes n_obs
+    _gpus()
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
+        image_bytes = lambda pb: int(L.pg_ld_image_bytes(n, pb + wk))
+        pb = _fit_batch(ctx, snp_batch, min(_LD_BATCH, _lm_batch(src)), p, 128, lambda pb: 20 * p + image_bytes(pb) + 2 * pb * src.row_bytes,
+                        f"ld_scores: n={n}, p={p}, window of {w} SNPs", "20 p bytes of sums and reach, an int8 image of snp_batch + window SNPs, two batch slots")
+        pe = pb + wk
+        image = ctx.alloc(image_bytes(pb))
+        dsum, dnp, dno = ctx.alloc(8 * p), ctx.alloc(4 * p), ctx.alloc(4 * p)
+        dreach = ctx.to_device(reach.astype(np.int32))
+        for buf in (dsum, dnp, dno):
+            _lib.check(L.pg_memset(ctx.handle, buf.ptr, 0, buf.nbytes), "pg_memset")
+        base = have = emitted = 0          # the image holds SNPs [base, base + have); rows [0, emitted) have met their forward partners
+        for s, e, slot in feed.batches(pb):
+            _call_dev(L, "pg_ld_encode_{}_dev", src, (ctx.handle, n, e - s), slot, e - s, (image.ptr, pe, have))
+            have += e - s
+            rows = (p if e == p else max(emitted, base + have - wk)) - emitted
+            if rows > 0:
+                _lib.check(L.pg_ld_score_dev(ctx.handle, n, image.ptr, pe, emitted - base, rows, have, wk, dreach.ptr + 4 * base, int(bool(adjust)),
+                                             dsum.ptr + 8 * base, dnp.ptr + 4 * base, dno.ptr + 4 * base), "pg_ld_score_dev")
+                emitted += rows
+            keep = base + have - emitted       # the SNPs whose rows are still to come: at most the largest reach
+            if e < p and have > keep:
+                _lib.check(L.pg_ld_shift_dev(ctx.handle, n, image.ptr, pe, have - keep, keep), "pg_ld_shift_dev")
+                base, have = base + have - keep, keep
+            _log(verbose - 1, f"ld_scores: SNPs [{s},{e}) queued")
+        ctx.sync()
+        tot, npairs, nobs = dsum.download((p,), np.int64), dnp.download((p,), np.int32), dno.download((p,), np.int32)
+    _stream_stats(stats, src, pb, t0)
+    if stats is not None:
+        stats["w"] = w
+    _log(verbose, f"LD scores: {p} SNPs, window of {w} SNPs, with {n} individuals in {time.time() - t0:.3f} s")
+    out = {"l2": np.where(nobs > 0, 1.0 + tot / 2.0 ** 32, np.nan), "n_pairs": npairs.astype(np.int64), "n_obs": nobs.astype(np.int64),
+           "reach_fwd": reach}
+    return _frame(out, _LDS_COLS, snps)
+
+
+LdscResult = namedtuple("LdscResult", "h2 h2_se intercept intercept_se mean_chi2 lambda_gc ratio m n_used")
+
+
+def _ldsc_sums(x, y, wt, edges):
+    """Per block [edges[b], edges[b + 1]) the weighted sums a line fit needs: columns w, w x, w x^2, w y, w x y."""
+    terms = np.stack([wt, wt * x, wt * x * x, wt * y, wt * x * y], axis=1)
+    return np.add.reduceat(terms, edges[:-1], axis=0)
+
+
+def _ldsc_solve(S, a):
+    """(slope, intercept) of the weighted line from rows of sums (_ldsc_sums); with a fixed intercept `a` the slope of y - a through 0."""
+    sw, sx, sxx, sy, sxy = (S[..., t] for t in range(5))
+    if a is not None:
+        return (sxy - a * sx) / sxx, np.full_like(sxx, a)
+    slope = (sw * sxy - sx * sy) / (sw * sxx - sx * sx)
+    return slope, (sy - slope * sx) / sw
+
+
+def ldsc(chi2, l2, n, *, m=None, blocks=200, intercept=None):
+    """LD score regression (Bulik-Sullivan et al. 2015): E[chi2_j] = a + N_j h2 l2_j / M over the SNPs of a scan.  The intercept a
+    measures confounding (population structure, cryptic relatedness: 1 without), the slope gives the SNP heritability h2; lambda_GC
+    alone cannot tell the two apart.
+
+    chi2: the 1-df association statistics of a scan frame, df["F_wald"] or (df["beta"] / df["se_beta"]) ** 2; l2: lmm.ld_scores(X,
+    ...)["l2"] of the same SNPs in the same order; n: the sample size, one number or one per SNP.  The SNPs where chi2, l2 and n are
+    all finite are used (n_used of them); M = `m`, or their count.  Host-only NumPy:
+      start      a = 1, h2 = clip(M (mean chi2 - 1) / mean(N l2), 0, 1); with `intercept` given a is that value here too (mean chi2 - a:
+                 the one place this goes beyond the written model, as ldsc does for a constrained intercept)
+      weights    w_j = 1 / (max(l2_j, 1) 2 (a + N_j h2 max(l2_j, 1) / M)^2) with the current (a, h2), h2 not clipped after the
+                 start: one over the LD score (correlated SNPs are counted l2 times) times the variance of a chi-square with that mean
+      updates    exactly two weighted least-squares fits of (h2, a), the weights recomputed before each; with `intercept` given it
+                 stays fixed and chi2 - a is regressed on N l2 / M without a constant
+      errors     a delete-one block jackknife over `blocks` contiguous blocks of the used SNPs (np.array_split's sizes), the weights
+                 of the last update held fixed
+    Returns an LdscResult: h2, h2_se, intercept, intercept_se (NaN when fixed), mean_chi2, lambda_gc = median chi2 / 0.4549...,
+    ratio = (a - 1) / (mean chi2 - 1) (the share of the inflation that is confounding; NaN at mean chi2 = 1), m, n_used.
+    Refused with ValueError: inputs that are not 1-D of one length, blocks < 2 or more blocks than used SNPs, m <= 0."""
+    y, ell = np.asarray(chi2, np.float64), np.asarray(l2, np.float64)
+    if y.ndim != 1 or ell.shape != y.shape:
+        raise ValueError(f"shape mismatch: chi2 has shape {y.shape}, l2 {ell.shape}")
+    nn = np.asarray(n, np.float64)
+    if nn.ndim == 0:
+        nn = np.full(y.shape, float(nn))
+    if nn.shape != y.shape:
+        raise ValueError(f"shape mismatch: n has shape {nn.shape} for {len(y)} SNPs")
+    if isinstance(blocks, bool) or not isinstance(blocks, (int, np.integer)):
+        raise ValueError(f"blocks must be an integer, not {blocks!r}")
+    use = np.isfinite(y) & np.isfinite(ell) & np.isfinite(nn)
+    y, ell, nn = y[use], ell[use], nn[use]
+    used = len(y)
+    if blocks < 2 or blocks > used:
+        raise ValueError(f"blocks must lie in [2, {used}] for {used} usable SNPs, not {blocks}")
+    M = float(used if m is None else m)
+    if not M > 0:
+        raise ValueError(f"m must be positive, not {m!r}")
+    fixed = None if intercept is None else float(intercept)
+    x, lw = nn * ell / M, np.maximum(ell, 1.0)
+    edges = np.concatenate([[0], np.cumsum([len(part) for part in np.array_split(np.arange(used), blocks)])])
+    whole = np.array([0, used])
+    a = 1.0 if fixed is None else fixed
+    h2 = float(np.clip(M * (y.mean() - a) / (nn * ell).mean(), 0.0, 1.0))
+    for _ in range(2):
+        wt = 1.0 / (lw * 2.0 * (a + nn * h2 * lw / M) ** 2)
+        slope, const = _ldsc_solve(_ldsc_sums(x, y, wt, whole)[0], fixed)
+        h2, a = float(slope), float(const)
+    S = _ldsc_sums(x, y, wt, edges)
+    dh, da = _ldsc_solve(S.sum(axis=0) - S, fixed)          # the fits without block b
+    se = lambda d: float(np.sqrt((blocks - 1) / blocks * ((d - d.mean()) ** 2).sum()))
+    mean = float(y.mean())
+    return LdscResult(h2, se(dh), a, float("nan") if fixed is not None else se(da), mean, float(np.median(y)) / _CHI2_1DF_MEDIAN,
+                      (a - 1.0) / (mean - 1.0) if mean != 1.0 else float("nan"), M, used)
 
 
 # ---- KING-robust relatedness and sample QC (csrc/king.hip, DESIGN §4.13) -------------------------------------------------------------------
