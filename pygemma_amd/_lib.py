@@ -15,6 +15,10 @@ LIB_PATH = os.environ.get("PYGEMMA_HIP_LIB") or os.path.join(_HERE, "lib", "libp
 _lib = None
 
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pygemma_hip.h")
+VC_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpygemma_vc.so")     # the variance-component unit: a library of its own
+VC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pygemma_vc.h")
+VC_SYMBOLS = []  # the functions VC_HEADER declares, in its order: filled by load_vc()
+_vc = None
 SYMBOLS = []     # the functions HEADER declares, in its order: filled by load()
 _CTYPES = {"int": C.c_int, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
 
@@ -74,6 +78,28 @@ def load():
     SYMBOLS[:] = [fn for fn, _, _ in decls]
     _lib = L
     return L
+
+
+def load_vc():
+    """Load libpygemma_vc.so (csrc/vc.hip: lmm.reml's kernels) beside the main library, which it needs, and bind it from
+    include/pygemma_vc.h.  Called by lmm.reml and lmm.vc_kinship, not at import: a process that fits no variance components
+    never maps it."""
+    global _vc
+    if _vc is not None:
+        return _vc
+    load()
+    for path in (VC_LIB_PATH, VC_HEADER):
+        if not os.path.exists(path):
+            raise PgError(f"{path} not found: build the HIP extension (python -c 'import __graft_entry__ as g; g.build()')")
+    V = C.CDLL(VC_LIB_PATH)
+    with open(VC_HEADER) as hdr:
+        decls = parse_header(hdr.read())
+    for fn, restype, argtypes in decls:
+        f = getattr(V, fn)
+        f.restype, f.argtypes = restype, argtypes
+    VC_SYMBOLS[:] = [fn for fn, _, _ in decls]
+    _vc = V
+    return V
 
 
 def check(rc, what=""):

@@ -39,10 +39,11 @@ from .bed import PackedBed
 from .ops import LM_COLS as _LM_COLS, _ldx
 from .model import *          # noqa: F401,F403  (precompute_mat, calc_lambda_restricted, newton, the *_overload scalars)
 from . import model as _model
+from .vc import RemlResult, reml, vc_kinship     # noqa: F401  (re-exported: variance components for several kinship matrices)
 
 __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
            "kinship", "ld", "ld_window", "ld_prune", "clump", "ld_scores", "ldsc", "LdscResult", "prs", "prs_weights", "king", "ibs",
-           "sample_stats", "related_pairs", "unrelated", "pca", "pca_project", "PcaResult"] + _model.__all__
+           "sample_stats", "related_pairs", "unrelated", "pca", "pca_project", "PcaResult", "reml", "vc_kinship", "RemlResult"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
 _BATCH_SNPS = 32768      # SNPs per batch at most: the unit of copy/compute overlap and of checkpointing
