@@ -296,6 +296,51 @@ int pg_ld_band_dev(pg_ctx *ctx, int64_t n, const void *image, int64_t pe, int64_
 int pg_ld_score_dev(pg_ctx *ctx, int64_t n, const void *image, int64_t pe, int64_t j0, int64_t rows, int64_t have, int64_t w,
                     const int32_t *reach, int adjust, int64_t *sum, int32_t *npairs, int32_t *nobs);
 
+/* ---- Pairwise SNP x SNP interaction (epistasis) on the int8 matrix pipe (csrc/epistasis.hip): the allele-table odds-ratio
+ * test of PLINK's --fast-epistasis over every pair of two windows of SNPs, reduced on the device to the pairs above a chi2 cut and a
+ * per-SNP summary.  Samples carry a group: 1 case, 0 control, any other value in neither.  With x, m of a SNP as LD defines them (hard
+ * calls only; a SNP that is not hard-call is all missing) a pair (a, b) has per group G four int32 sums over the samples of G,
+ *     N = sum m_a m_b   Sa = sum x_a m_b   Sb = sum m_a x_b   Sab = sum x_a x_b
+ * then exactly in int64 the allele table  A = 4 N - 2 Sa - 2 Sb + Sab,  B = 2 Sb - Sab,  C = 2 Sa - Sab,  D = Sab.  The group is DEFINED
+ * for the pair when A + B, C + D, A + C and B + D are all positive.  Doubled cells t = 2 cell + z with z = 1 when any of the four cells is
+ * 0 (1/2 added to every cell), else 0; in fp64, every operation rounded once,
+ *     L = log(((double)tA (double)tD) / ((double)tB (double)tC))      v = (2 / tA + 2 / tD) + (2 / tB + 2 / tC)
+ * PG_EPI_CASE_CONTROL: z = (L1 - L0) / sqrt(v1 + v0), defined when both groups are; PG_EPI_CASE_ONLY: z = L1 / sqrt(v1), defined when
+ * the cases are.  chi2 = z z on 1 df.  z(a, b) and z(b, a) are the same bits.
+ *   image   : pg_epi_image_bytes(n, pe) device bytes on a 16-byte boundary, opaque: six int8 planes x [g=1], x [g=0], m [g=1], m [g=0],
+ *             x [g>=0], m [g>=0] of pe SNP-major rows with the LD image's row pitch, zero past sample n; per SNP {sum x in cases, sum x
+ *             in controls, called cases, called controls} and a flag "a missing call among the cases and controls"; the group sizes.
+ *   pg_epi_split_dev : writes the SNP positions [from, from + count) of an epistasis image for pe from the same positions of an LD
+ *             image for pe (pg_ld_encode_{bed,x}_dev) and the int8 group[n] (device memory).  Every SNP of an image, and both images of a
+ *             pg_epi_block_dev call, must have been split with the same group vector.
+ *   pg_epi_block_dev : visits the pairs (a0 + ia of image A, b0 + ib of image B), ia < na, ib < nb (A and B may be the same image).
+ *             The pair's SNPs carry the GLOBAL indices ga0 + ia and gb0 + ib (32-bit): the hit records, `best` and the per-SNP arrays
+ *             speak in them (with ga0 = a0, gb0 = b0 that is the image position, as in pg_ld_score_dev).  upper != 0: only the pairs
+ *             with ga0 + ia < gb0 + ib are visited; tile pairs wholly on or below the diagonal return at once.
+ *   count, hits, cap : a visited, defined pair with chi2 >= chi2_min takes the next slot of the 64-bit counter *count (the caller
+ *             zeroes it; it counts every hit) and, while slot < cap, is written as the 16-byte record {int32 a, int32 b, double z}
+ *             at hits[slot], in no particular order.  Nothing is written at or past cap; hits may be NULL when cap = 0.
+ *   n_tot, n_sig, best : each or NULL; indexed by global index, accumulated with integer atomics (the caller zeroes them once): a
+ *             defined pair adds 1 to n_tot of both of its SNPs, a hit 1 to n_sig of both, and best[s] becomes the maximum of
+ *             (float32 bits of (float)chi2) << 32 | ~partner (32 bits) over the defined pairs of s: the same bits in any order, ties
+ *             to the smaller partner.
+ *   sums    : or NULL; eight int32 of every VISITED pair at sums[8 (ia nb + ib) + t], t in the order N, Sa, Sb, Sab of the cases, then
+ *             of the controls.  Nothing outside the na x nb window is written.
+ * A tile pair (128 SNPs of A, 256 of B) without a missing call among the cases and controls takes one int8 product (N the group's
+ * size, Sa and Sb from the per-SNP totals), any other four products over the masked planes: the same integers either way
+ * (PG_EPI_PLANES=1 in the environment sends every tile pair the second way; tests and A/B timing only).
+ * PG_EINVAL for NULL pointers (ctx, images, group, count, hits with cap > 0), an image or hits off 16 bytes, count or best off 8, n < 1,
+ * n >= 2^28, negative counts or indices, windows outside their images, a global index of 2^31 or more, cap < 0, chi2_min negative
+ * or not finite; PG_ENOTSUP for an unknown mode: a refused call enqueues nothing.  pg_epi_image_bytes is 0 for n or pe out of range. */
+#define PG_EPI_CASE_CONTROL 0
+#define PG_EPI_CASE_ONLY 1
+size_t pg_epi_image_bytes(int64_t n, int64_t pe);
+int pg_epi_split_dev(pg_ctx *ctx, int64_t n, const void *ld_image, int64_t pe, int64_t from, int64_t count, const signed char *group,
+                     void *epi_image);
+int pg_epi_block_dev(pg_ctx *ctx, int64_t n, const void *A, int64_t pea, int64_t a0, int64_t na, int64_t ga0, const void *B, int64_t peb,
+                     int64_t b0, int64_t nb, int64_t gb0, int mode, int upper, double chi2_min, uint64_t *count, void *hits, int64_t cap,
+                     int32_t *n_tot, int32_t *n_sig, uint64_t *best, int32_t *sums);
+
 /* ---- Polygenic scores from RAW genotypes on the fp64 matrix pipe (csrc/prs.hip): S = G W, PLINK's --score, accumulated over
  * the SNP batches of a stream.  Block conventions of pg_snp_stats_x_dev / pg_snp_stats_bed_dev: an (n x pb) sample-major (snp_major = 0,
  * ldX >= pb) or (pb x n) SNP-major (ldX >= n) block of dtype PG_DTYPE_*, or pb packed .bed records (ldb >= ceil(n/4) bytes; code

@@ -24,13 +24,13 @@
 // each within a reach of its row, as r^2 in fixed point summed per SNP (LD scores, pg_ld_score_dev).
 #include "geno_src.hpp"
 #include "i8_pair.hpp"
+#include "ld_layout.hpp"
 
 #include <cmath>
 #include <type_traits>
 
 namespace pg {
 
-constexpr int LD_BK = I8P_BK;     // samples per K-tile
 constexpr int LD_T1 = 252;        // SNPs per tile side, one-product path
 constexpr int LD_T3 = 84;         // SNPs per sub-tile side, three-plane path: 2 halves x 42 SNPs x 3 planes
 constexpr int LD_H3 = 42;
@@ -38,19 +38,6 @@ constexpr long long LD_MAXN = 1LL << 28;      // exclusive: every sum fits int32
 constexpr long long LD_MAXPE = 1LL << 31;
 constexpr long long LD_SCORE_MAXW = 1LL << 28;      // exclusive: a SNP's 2 w pairs of at most 2^32 each stay inside int64
 
-struct LdLayout {
-    long long ldk;
-    size_t plane, totals, total;
-};
-static LdLayout ld_layout(long long n, long long pe)
-{
-    LdLayout L;
-    L.ldk = (n + LD_BK - 1) / LD_BK * LD_BK;
-    L.plane = (size_t)pe * L.ldk;
-    L.totals = (3 * L.plane + 255) & ~(size_t)255;
-    L.total = L.totals + (size_t)pe * 16 + 256;
-    return L;
-}
 
 // ---- encode -----------------------------------------------------------------------------------------------------------------------------
 // one element -> code, called, not-a-hard-call

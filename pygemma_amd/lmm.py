@@ -22,6 +22,7 @@ There is no CPU fallback: without the HIP library or a GPU this raises.
 import contextlib
 import ctypes as C
 import json
+import math
 import os
 import threading
 import time
@@ -42,7 +43,7 @@ from . import model as _model
 from .vc import RemlResult, reml, vc_kinship     # noqa: F401  (re-exported: variance components for several kinship matrices)
 
 __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
-           "kinship", "ld", "ld_window", "ld_prune", "clump", "ld_scores", "ldsc", "LdscResult", "prs", "prs_weights", "king", "ibs",
+           "kinship", "ld", "ld_window", "ld_prune", "clump", "ld_scores", "ldsc", "LdscResult", "epistasis", "EpistasisResult", "prs", "prs_weights", "king", "ibs",
            "sample_stats", "related_pairs", "unrelated", "pca", "pca_project", "PcaResult", "reml", "vc_kinship", "RemlResult"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
@@ -1271,6 +1272,166 @@ def ldsc(chi2, l2, n, *, m=None, blocks=200, intercept=None):
     mean = float(y.mean())
     return LdscResult(h2, se(dh), a, float("nan") if fixed is not None else se(da), mean, float(np.median(y)) / _CHI2_1DF_MEDIAN,
                       (a - 1.0) / (mean - 1.0) if mean != 1.0 else float("nan"), M, used)
+
+
+# ---- pairwise SNP x SNP interaction (csrc/epistasis.hip) ------------------------------------------------------------------------
+EpistasisResult = namedtuple("EpistasisResult", "pairs summary chi2_min")
+_EPI_P = 1e-4                  # the default cut, as the object the signature holds: `p` left alone is told from p=1e-4 given beside `chi2`
+_EPI_CAP = 1 << 22             # hit records (16 bytes each) a block pair's buffer holds before the pair is rerun with the counted size
+_EPI_HIT = np.dtype([("a", "<i4"), ("b", "<i4"), ("z", "<f8")])
+_EPI_MAX_SNPS = 2 ** 31 - 1
+
+
+def _epi_chi2_min(p, chi2):
+    """The chi2 cut of an epistasis scan: `chi2` when given, else the 1-df chi2 whose upper tail is p, by bisection on erfc(z / sqrt 2) = p
+    (z in [0, 40]; erfc underflows beyond) down to neighbouring doubles."""
+    if chi2 is not None:
+        if p is not _EPI_P:
+            raise ValueError("give the cut as p or as chi2, not both")
+        if isinstance(chi2, bool) or not isinstance(chi2, (int, float, np.integer, np.floating)) or not (np.isfinite(chi2) and chi2 >= 0):
+            raise ValueError(f"chi2 must be a finite number >= 0, not {chi2!r}")
+        return float(chi2)
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0 < p <= 1:
+        raise ValueError(f"p must lie in (0, 1], not {p!r}")
+    lo, hi = 0.0, 40.0                          # erfc(lo / sqrt 2) >= p > erfc(hi / sqrt 2)
+    if p == 1:
+        return 0.0
+    if math.erfc(hi / math.sqrt(2.0)) >= p:
+        return hi * hi
+    while True:
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:
+            return lo * lo
+        if math.erfc(mid / math.sqrt(2.0)) >= p:
+            lo = mid
+        else:
+            hi = mid
+
+
+def _epi_group(y, n, case_only):
+    """The int8 group of every sample from a 0/1 phenotype: 1 case, 0 control, -1 (NaN) in neither."""
+    y = np.asarray(y)
+    if y.ndim == 2 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.ndim != 1 or y.shape[0] != n:
+        raise ValueError(f"shape mismatch: y has shape {y.shape} for {n} samples")
+    if y.dtype.kind not in "biuf":
+        raise ValueError(f"y must hold 0, 1 or NaN, not dtype {y.dtype}")
+    y = y.astype(np.float64)
+    if not (np.isnan(y) | (y == 0) | (y == 1)).all():
+        raise ValueError("y must hold 0 (control), 1 (case) or NaN (excluded) and nothing else")
+    if not (y == 1).any():
+        raise ValueError("y holds no case")
+    if not case_only and not (y == 0).any():
+        raise ValueError("y holds no control: a case/control test needs both (case_only=True tests the cases alone)")
+    return np.where(y == 1, 1, np.where(y == 0, 0, -1)).astype(np.int8)
+
+
+def epistasis(X, y, *, a=None, b=None, p=_EPI_P, chi2=None, case_only=False, snp_batch=None, device=0, verbose=0, stats=None):
+    """Pairwise SNP x SNP interaction scan of a case/control trait: PLINK's --fast-epistasis (the allele-table odds-ratio test) over
+    every pair of SNPs, on the int8 matrix pipe (csrc/epistasis.hip); only the pairs above the cut and a per-SNP summary leave the device.
+
+    X (n, p) as for `ld`: hard calls only, a SNP with another observed value counts as all missing.  y (n,): 1 case, 0 control (bool
+    allowed), NaN excluded.  `a`, `b`: masks or indices as for `ld`; the default is every pair i < j of all SNPs, `a` alone every pair
+    within the selection (earlier against later in its order), with `b` given every SNP of `a` (None: all) against every SNP of `b`.
+    For a pair and a group (cases, controls) the four int32 sums over the group's samples where both are called,
+      N = sum m_a m_b, Sa = sum x_a m_b, Sb = sum m_a x_b, Sab = sum x_a x_b
+    give the allele table A = 4N - 2Sa - 2Sb + Sab, B = 2Sb - Sab, C = 2Sa - Sab, D = Sab exactly; the group is defined when all four
+    margins are positive; when a cell is 0, 1/2 is added to every cell; in fp64 L = log(A D / (B C)), v = 1/A + 1/B + 1/C + 1/D, and
+    z = (L_case - L_control) / sqrt(v_case + v_control), or with `case_only` z = L_case / sqrt(v_case) (valid for SNPs in linkage
+    equilibrium in the population).  chi2 = z^2 on 1 df, p = erfc(|z| / sqrt 2).  z(a, b) = z(b, a), bit for bit.
+    The cut is on chi2: `chi2`, or the chi2 whose p-value is `p` (default 1e-4).  The SNPs are encoded once into a device image
+    (through the two-slot feed in batches of `snp_batch`), cut into blocks of `snp_batch` SNPs (default: all of them, when they fit),
+    and the block pairs I <= J are walked; a block pair with more hits than its buffer holds is rerun with a buffer of the counted size.
+    Returns an EpistasisResult:
+      pairs     DataFrame i, j (columns of X), z, chi2, p of the pairs with chi2 >= chi2_min, sorted by (i, j)
+      summary   DataFrame, a row per SNP of the selection (`a`, then `b` when given): snp, n_tot (defined pairs it is in), n_sig (those
+                above the cut), best_chi2 (float32; NaN without a defined pair), best_partner (-1 likewise; ties to the earlier
+                SNP of the selection): PLINK's .epi.cc.summary
+      chi2_min  the cut
+    `stats` receives blocks (block pairs), reruns, pairs_defined, bytes_in, seconds.  Refused with ValueError before any device work:
+    what `ld` refuses for X, `a`, `b`; y of another length or with values other than 0, 1, NaN; no case; no control unless
+    `case_only`; both `p` and `chi2`; p outside (0, 1]; a negative or non-finite chi2; a bad snp_batch."""
+    t0 = time.time()
+    _check_snp_batch(snp_batch)
+    chi2_min = _epi_chi2_min(p, chi2)
+    X = _ld_source(X, "epistasis")
+    group = _epi_group(y, X.shape[0], case_only)
+    XA, ia = _ld_take(X, a)
+    sets = b is not None
+    XB, ib = _ld_take(X, b) if sets else (XA, ia)
+    if len(ia) + (len(ib) if sets else 0) > _EPI_MAX_SNPS:
+        raise ValueError("epistasis indexes SNPs in int32: the selection holds 2^31 or more")
+    L = _lib.load()
+    _gpus()
+    srcs = [_describe(XA)] + ([_describe(XB)] if sets else [])
+    n, na, nb = srcs[0].n, len(ia), len(ib)
+    total = na + (nb if sets else 0)
+    cap = int(os.environ.get("PYGEMMA_EPI_CAP", _EPI_CAP))
+    nblocks = reruns = 0
+    found = []
+    with _lib.Context(device) as ctx:
+        dgroup = ctx.to_device(group)
+        images = []
+        for src in srcs:
+            ld_bytes, epi_bytes = int(L.pg_ld_image_bytes(n, src.p)), int(L.pg_epi_image_bytes(n, src.p))
+            pb = _fit_batch(ctx, snp_batch, _lm_batch(src), src.p, 128, lambda pb: ld_bytes + epi_bytes + 2 * pb * src.row_bytes + 16 * (cap + total),
+                            f"epistasis: n={n}, {src.p} SNPs", "int8 images 9 n bytes per SNP, two batch slots, the hit buffer")
+            ldim = ctx.alloc(ld_bytes)
+            _ld_encode(L, ctx, src, pb, ldim, src.p)
+            image = ctx.alloc(epi_bytes)
+            _lib.check(L.pg_epi_split_dev(ctx.handle, n, ldim.ptr, src.p, 0, src.p, dgroup.ptr, image.ptr), "pg_epi_split_dev")
+            ctx.sync()
+            ldim.free()
+            images.append(image)
+        imA, imB = images[0], images[-1]
+        dcount, dhits = ctx.alloc(8), ctx.alloc(16 * max(cap, 1))
+        dtot, dsig, dbest = ctx.alloc(4 * total), ctx.alloc(4 * total), ctx.alloc(8 * total)
+        for buf in (dtot, dsig, dbest):
+            _lib.check(L.pg_memset(ctx.handle, buf.ptr, 0, buf.nbytes), "pg_memset")
+        mode = 1 if case_only else 0
+        step = int(snp_batch or max(na, nb))
+
+        def block(a0, a1, b0, b1, hits, room, per_snp):
+            _lib.check(L.pg_memset(ctx.handle, dcount.ptr, 0, 8), "pg_memset")
+            _lib.check(L.pg_epi_block_dev(ctx.handle, n, imA.ptr, na, a0, a1 - a0, a0, imB.ptr, nb, b0, b1 - b0, (na if sets else 0) + b0, mode,
+                                          0 if sets else 1, chi2_min, dcount.ptr, hits.ptr, room, *(per_snp or (None, None, None)), None),
+                       "pg_epi_block_dev")
+            ctx.sync()
+            return int(dcount.download((1,), np.uint64)[0])
+
+        for a0 in range(0, na, step):
+            for b0 in range(0 if sets else a0, nb, step):
+                a1, b1 = min(a0 + step, na), min(b0 + step, nb)
+                count = block(a0, a1, b0, b1, dhits, cap, (dtot.ptr, dsig.ptr, dbest.ptr))
+                nblocks += 1
+                if count > cap:                    # the counter is exact: once more with room for all, the per-SNP arrays left alone
+                    big = ctx.alloc(16 * count)
+                    assert block(a0, a1, b0, b1, big, count, None) == count
+                    found.append(big.download((count,), _EPI_HIT))
+                    big.free()
+                    reruns += 1
+                elif count:
+                    found.append(dhits.download((count,), _EPI_HIT))
+                _log(verbose - 1, f"epistasis: SNPs [{a0},{a1}) x [{b0},{b1}): {count} pairs above the cut")
+        ntot, nsig, best = dtot.download((total,), np.int32), dsig.download((total,), np.int32), dbest.download((total,), np.uint64)
+    rec = np.concatenate(found) if found else np.empty(0, _EPI_HIT)
+    col = np.concatenate([ia, ib]) if sets else ia           # global index -> column of X
+    i, j, z = col[rec["a"]], col[rec["b"]], rec["z"]
+    order = np.lexsort((j, i))
+    i, j, z = i[order], j[order], z[order]
+    pairs = pd.DataFrame({"i": i, "j": j, "z": z, "chi2": z * z,
+                          "p": np.array([math.erfc(abs(v) / math.sqrt(2.0)) for v in z.tolist()], np.float64)})
+    some = ntot > 0
+    partner = (~best & np.uint64(0xffffffff)).astype(np.int64)
+    summary = pd.DataFrame({"snp": col, "n_tot": ntot.astype(np.int64), "n_sig": nsig.astype(np.int64),
+                            "best_chi2": np.where(some, (best >> np.uint64(32)).astype(np.uint32).view(np.float32), np.float32(np.nan)),
+                            "best_partner": np.where(some, col[np.where(some, partner, 0)], -1)})
+    if stats is not None:
+        stats.update({"blocks": nblocks, "reruns": reruns, "pairs_defined": int(ntot.sum(dtype=np.int64)) // 2,
+                      "bytes_in": sum(s.p * s.row_bytes for s in srcs), "seconds": time.time() - t0})
+    _log(verbose, f"epistasis: {na} x {nb} SNPs with {n} individuals, {len(pairs)} pairs at chi2 >= {chi2_min:.3f} in {time.time() - t0:.3f} s")
+    return EpistasisResult(pairs, summary, chi2_min)
 
 
 # ---- KING-robust relatedness and sample QC (csrc/king.hip, DESIGN §4.13) -------------------------------------------------------------------
