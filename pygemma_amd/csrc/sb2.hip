@@ -219,56 +219,10 @@ __device__ __forceinline__ void solve_rows_blocked(double *X, UC coef, UD rcp, i
     }
 }
 
-// ---- pass 1 of CholeskyQR2: G -> R1 (upper) and R1^-1, one wavefront, everything in registers -------------------------------
-// Lane j keeps column j of the matrix (64 doubles).  Right-looking Cholesky: at step k the pivot and the row R[k][i] reach every lane
-// through v_readlane (compile-time lane numbers: all loops are unrolled), no LDS, no barriers.  Then X R = I with lane i = row i of X,
-// the coefficient R[k][j] read from lane j's register k.  (The LDS version with run-time loops spent its time in LDS latency: 82 us;
-// the first, with workgroup barriers: 112 us.)
-__global__ __launch_bounds__(64) void chol_inv_kernel(const double *G, double *R, double *Rinv, int *fail)
-{
-    const int lane = threadIdx.x;
-    __builtin_amdgcn_s_setprio(3);     // runs beside the trailing update's MFMA waves (look-ahead): a latency chain, served first
-    double a[B], rc[B];
-#pragma unroll
-    for (int i = 0; i < B; i++) a[i] = G[i * B + lane];
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < B; k++) {
-        const double akk = readlane_d(a[k], k);
-        const bool bad = !(akk > 0.0) || !(akk < 1.0e300);
-        ok = ok && !bad;
-        const double d = bad ? 1.0 : sqrt(akk), rcp = 1.0 / d;
-        rc[k] = rcp;
-        const double rk = (lane > k) ? a[k] * rcp : ((lane == k) ? d : 0.0);     // R[k][lane]
-        a[k] = rk;
-#pragma unroll
-        for (int i = k + 1; i < B; i++) a[i] = fma(-readlane_d(rk, i), rk, a[i]);   // A[i][lane] -= R[k][i] R[k][lane]  (used for lane >= i)
-    }
-    if (!ok && lane == 0) atomicOr(fail, 1);
-    // X R = I through LDS (blocked: solve_rows_blocked; the register version — 2016 dependent v_readlane + FMA pairs — took as long
-    // as the factorisation itself)
-    extern __shared__ double lds[];
-    double *Rm = lds, *Xl = lds + MAT, *rcs = lds + 2 * MAT;
-#pragma unroll
-    for (int i = 0; i < B; i++) {
-        const double r = (lane >= i) ? a[i] : 0.0;
-        Rm[i * P65 + lane] = r;
-        R[i * B + lane] = r;
-        Xl[i * P65 + lane] = (i == lane) ? 1.0 : 0.0;
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < B; k++) rcs[k] = rc[k];
-    }
-    wave_sync_lds();
-    solve_rows_blocked(Xl, [&](int k, int j) { return Rm[k * P65 + j]; }, [&](int j) { return rcs[j]; }, lane);
-#pragma unroll
-    for (int i = 0; i < B; i++) Rinv[i * B + lane] = (lane >= i) ? Xl[i * P65 + lane] : 0.0;
-}
-
-// ---- pass 1, blocked (r4): the same R1 and R1^-1 in ~13 us instead of 47 ----------------------------------------------------------
-// chol_inv_kernel above is 2 016 dependent (two v_readlane + FMA) steps in one wavefront, fully unrolled (~50 KB of code: beside
-// another kernel its instruction fetches alone made it 2 - 3 x slower).  Here the factorisation walks four row panels of 16 rows: ONE
+// ---- pass 1 of CholeskyQR2, blocked (r4): G -> R1 (upper) and R1^-1 in ~13 us ------------------------------------------------------
+// (The whole 64 x 64 factorisation in the registers of one wavefront takes 47 us: 2 016 dependent (two v_readlane + FMA) steps, fully
+// unrolled into ~50 KB of code whose instruction fetches alone make it 2 - 3 x slower beside another kernel.)  Here the factorisation
+// walks four row panels of 16 rows: ONE
 // wavefront holds the panel's 16 x 64 entries with lane = COLUMN and runs the 16 elimination steps of the panel on all columns at once
 // (120 readlane + FMA pairs per panel: the multipliers R[k][i] are wave-uniform), which yields the panel's rows of R — diagonal block and
 // everything right of it — without a separate triangular solve; the trailing blocks are updated as 16 x 16 x 16 MFMA products by all
@@ -411,10 +365,10 @@ __global__ __launch_bounds__(256) void chol_inv16_kernel(const double *G, double
 __global__ __launch_bounds__(256) void recon_kernel(const double *G2, const double *R1g, const double *Q1top, double *Aband, long long lda,
                                                     double *VW, double *Vst, long long ldv, double *Tout, double *Xm, double *Rprod, int *fail)
 {
-    // three LDS matrices (100 KB: the kernel has to find room on a CU beside the workgroups of the trailing update it overlaps):
+    // three LDS matrices (100 KB):
     // M0: G2 -> R2 -> T;   M1: R2^-1 -> Xm (in place);   M2: R1 -> top block of Q -> its LU
     extern __shared__ double lds[];
-    __builtin_amdgcn_s_setprio(3);     // runs beside the trailing update's MFMA waves (look-ahead): a latency chain, served first
+    __builtin_amdgcn_s_setprio(3);     // a latency chain: served first wherever other waves share its SIMDs
     double *M0 = lds, *M1 = lds + MAT, *M2 = lds + 2 * MAT;
     __shared__ double Dg[B], piv[B], prc[B];
     __shared__ double red[4];
@@ -624,14 +578,6 @@ __global__ __launch_bounds__(256) void transpose_vw_kernel(long long m, const do
     __syncthreads();
     for (int c = ty; c < 64; c += 4)
         if (r0 + tx < m) VWt[(long long)(c0 + c) * ldt + r0 + tx] = tile[tx][c];
-}
-
-// rows [r_begin, m) of the panel's V (VW columns 0..63) into the reflector store
-__global__ void copy_v_kernel(long long m, long long r_begin, const double *VW, double *Vst, long long ldv)
-{
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long r = r_begin + idx / B, c = idx % B;
-    if (r < m) Vst[r * ldv + c] = VW[r * (2 * B) + c];
 }
 
 // ---- fused panel kernels (r4): the chain of thin products between the two big GEMMs of a panel ------------------------------------
@@ -874,54 +820,12 @@ __global__ __launch_bounds__(256) void panel_w_kernel(long long m, const double 
     store64_transposed(Ts, VWt + (size_t)B * ldt, ldt, r0, rows, tid);
 }
 
-// The two-sided update restricted to the NEXT panel's 64 columns (look-ahead): C (m x 64, row stride ldc: rows = the whole trailing matrix,
-// columns = its first 64) -= V W_top' + W V_top', with [V W] the current panel's block vectors (m x 128, row stride 2b) and _top their first
-// 64 rows.  One workgroup per 64 rows; 128 MFMAs per wavefront.  The full update then leaves these columns alone.
-__global__ __launch_bounds__(256) void panel_next_update_kernel(long long m, const double *VW, double *C, long long ldc)
-{
-    extern __shared__ double lds[];
-    double *Vb = lds, *Wb = lds + MAT, *WtT = lds + 2 * MAT, *VtT = lds + 3 * MAT;      // V_b, W_b (negated) | W_top', V_top' (k-major)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, k4 = lane >> 4;
-    const long long r0 = (long long)blockIdx.x * B;
-    const int rows = (int)((m - r0 < B) ? m - r0 : B);
-    {
-        const int i = tid >> 2, j0 = (tid & 3) * 16;
-#pragma unroll
-        for (int q = 0; q < 16; q++) {
-            const double v = (i < rows) ? VW[(r0 + i) * (2 * B) + j0 + q] : 0.0, w_ = (i < rows) ? VW[(r0 + i) * (2 * B) + B + j0 + q] : 0.0;
-            Vb[i * P65 + j0 + q] = -v;
-            Wb[i * P65 + j0 + q] = -w_;
-            // top block, transposed: WtT[k][c] = W[c][k], VtT[k][c] = V[c][k]   (i = c here; the panel has more than 64 rows)
-            WtT[(j0 + q) * P65 + i] = VW[(long long)i * (2 * B) + B + j0 + q];
-            VtT[(j0 + q) * P65 + i] = VW[(long long)i * (2 * B) + j0 + q];
-        }
-    }
-    doublex4 acc[4];
-#pragma unroll
-    for (int tj = 0; tj < 4; tj++)
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int i = 16 * wave + k4 + 4 * e;
-            acc[tj][e] = (i < rows) ? C[(r0 + i) * ldc + 16 * tj + r16] : 0.0;
-        }
-    __syncthreads();
-    mm64_mfma_acc(Vb, WtT, acc, tid);
-    mm64_mfma_acc(Wb, VtT, acc, tid);
-#pragma unroll
-    for (int tj = 0; tj < 4; tj++)
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int i = 16 * wave + k4 + 4 * e;
-            if (i < rows) C[(r0 + i) * ldc + 16 * tj + r16] = acc[tj][e];
-        }
-}
-
 // =================================================================================================================================
-// doubles of the stage-1 panel work space: two transposed copies [V W]' (128 x ldt each) + one 64 x 64 Gram partial per block of 64 rows
+// doubles of the stage-1 panel work space: the transposed copy [V W]' (128 x ldt) + one 64 x 64 Gram partial per block of 64 rows
 static size_t sb2_panel_work(int n)
 {
     const size_t ldt = ((size_t)n + 128 + 127) / 128 * 128;
-    return 2 * 128 * ldt + ((size_t)n / B + 2) * B * B;
+    return 128 * ldt + ((size_t)n / B + 2) * B * B;
 }
 size_t sb2_bytes(int n)
 {
@@ -988,12 +892,11 @@ void sb2_free(Sb2Work &w)
 int sy2sb_device(pg_ctx *ctx, int n, double *A, Sb2Work &w)
 {
     hipStream_t st = ctx->stream;
-    constexpr int LDS4 = 4 * MAT * 8, CHOL_LDS = (2 * MAT + B) * 8, CHOL16_LDS = (2 * MAT + B) * 8;
+    constexpr int LDS4 = 4 * MAT * 8, CHOL16_LDS = (2 * MAT + B) * 8;
     // the dynamic-LDS limit is a per-DEVICE property of the function: set on every call (a few microseconds, once per solve), never
     // cached per process — a second device in the same process would launch these kernels without it
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&recon_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS4));
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&small_qr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS4));
-    PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&chol_inv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CHOL_LDS));
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&chol_inv16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CHOL16_LDS));
     PG_HIP(hipMemsetAsync(w.Vst, 0, (size_t)n * n * 8, st));
     PG_HIP(hipMemsetAsync(w.Tst, 0, (size_t)(w.npan + 1) * B * B * 8, st));
@@ -1004,199 +907,89 @@ int sy2sb_device(pg_ctx *ctx, int n, double *A, Sb2Work &w)
     PG_HIP(hipMemsetAsync(w.VW, 0, (size_t)128 * 2 * B * 8, st));
     double *const VW0 = w.VW + (size_t)128 * 2 * B, *const Qb0 = w.Qb + (size_t)128 * B;
     // transposed copy of [V W] for the rank-128 update (the back-transformation's work space is free during stage 1): 128 rows of
-    // ldt doubles, the panel's rows from column 128 on, the 128 columns in front kept zero
+    // ldt doubles, the panel's rows from column 128 on, the 128 columns in front kept zero.  One copy serves every panel: stream order
+    // puts a panel's update before the next panel's panel_v_kernel, which overwrites it.  Behind it the Gram partials of the fused
+    // panel kernels: one 64 x 64 block per 64 rows
     const long long ldt = ((long long)n + 128 + 127) / 128 * 128;
-    // two copies, used by alternating panels (with look-ahead the next panel's V is written while the update still reads this one's),
-    // then the Gram partials of the fused panel kernels: one 64 x 64 block per 64 rows
-    double *const VWt_base = w.Pw;
-    auto VWt_of = [&](int pan_) { return VWt_base + (size_t)(pan_ & 1) * 128 * ldt; };
-    double *const parts = VWt_base + (size_t)2 * 128 * ldt;
-    PG_HIP(hipMemsetAsync(VWt_base, 0, (size_t)2 * 128 * ldt * 8, st));
-    bool chol16 = true;      // the blocked first-pass Cholesky (PG_SB2_CHOL16=0: the one-wavefront version)
-    if (const char *e_ = getenv("PG_SB2_CHOL16")) chol16 = atoi(e_) != 0;
-    bool fused = n >= 2 * B + 2;
-    if (const char *e_ = getenv("PG_SB2_FUSED")) fused = fused && atoi(e_) != 0;      // A/B timing and tests
+    double *const VWt = w.Pw;
+    double *const parts = VWt + (size_t)128 * ldt;
+    PG_HIP(hipMemsetAsync(VWt, 0, (size_t)128 * ldt * 8, st));
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gram_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * MAT * 8));
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gram_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * MAT * 8));
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_v_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * MAT * 8));
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_xy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * MAT * 8));
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * MAT * 8));
-    PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_next_update_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * MAT * 8));
     double *sm = w.sm;
     auto SM = [&](int k) { return sm + (size_t)k * B * B; };
     const long long ld = n;
-    // factorisation of the panel at column j (everything that needs only the panel's own columns): on the stream of context c
-    auto factor = [&](pg_ctx *c, int j, int pan) -> int {
-        hipStream_t cs = c->stream;
+    // factorisation of the panel at column j (everything that needs only the panel's own columns)
+    auto factor = [&](int j, int pan) -> int {
         const long long m = n - j - B;
         double *P = A + (size_t)(j + B) * ld + j;                 // m x 64 panel below the diagonal block
         double *Vs = w.Vst + (size_t)(j + B) * ld + j;
         double *Tp = w.Tst + (size_t)pan * B * B;
-        int rc = PG_OK;
-        if (m > B && fused) {
+        if (m > B) {
             // CholeskyQR2 with the fused panel kernels: Gram partials per block of 64 rows + their sum; R1, R1^-1; Q1 = P R1^-1 and the
             // partials of G2 = Q1'Q1 in one kernel; reconstruction; V = Q1 Xm straight into [V W], the reflector store and [V W]'
             const unsigned nb = (unsigned)((m + B - 1) / B);
-            panel_gram_kernel<false><<<nb, 256, 2 * MAT * 8, cs>>>(m, P, ld, nullptr, nullptr, parts);
-            sum_partials_kernel<<<B * B / 32, 256, 0, cs>>>((int)nb, parts, SM(SM_G1));
-            if (chol16) chol_inv16_kernel<<<1, 256, CHOL16_LDS, cs>>>(SM(SM_G1), SM(SM_R1), SM(SM_R1INV), w.fail);
-            else chol_inv_kernel<<<1, 64, CHOL_LDS, cs>>>(SM(SM_G1), SM(SM_R1), SM(SM_R1INV), w.fail);
-            panel_gram_kernel<true><<<nb, 256, 2 * MAT * 8, cs>>>(m, P, ld, SM(SM_R1INV), Qb0, parts);
-            sum_partials_kernel<<<B * B / 32, 256, 0, cs>>>((int)nb, parts, SM(SM_G2));
-            recon_kernel<<<1, 256, 3 * MAT * 8, cs>>>(SM(SM_G2), SM(SM_R1), Qb0, P, ld, VW0, Vs, ld, Tp, SM(SM_XM), SM(SM_RPROD), w.fail);
-            panel_v_kernel<<<nb, 256, 3 * MAT * 8, cs>>>(m, Qb0, SM(SM_XM), VW0, Vs, ld, VWt_of(pan) + 128, ldt);
-        } else if (m > B) {
-            // CholeskyQR2: G1 = P'P, R1; Q1 = P R1^-1; G2 = Q1'Q1, R2; (Q = Q1 R2^-1 only through its top block and Xm)
-            rc = dgemm(c, true, B, B, m, 1.0, P, ld, P, ld, 0.0, SM(SM_G1), B);
-            if (rc) return rc;
-            chol_inv_kernel<<<1, 64, CHOL_LDS, cs>>>(SM(SM_G1), SM(SM_R1), SM(SM_R1INV), w.fail);
-            rc = dgemm(c, false, m, B, B, 1.0, P, ld, SM(SM_R1INV), B, 0.0, Qb0, B);
-            if (!rc) rc = dgemm(c, true, B, B, m, 1.0, Qb0, B, Qb0, B, 0.0, SM(SM_G2), B);
-            if (rc) return rc;
-            recon_kernel<<<1, 256, 3 * MAT * 8, cs>>>(SM(SM_G2), SM(SM_R1), Qb0, P, ld, VW0, Vs, ld, Tp, SM(SM_XM), SM(SM_RPROD), w.fail);
-            // rows 64.. of V = Q1[64:, :] Xm  -> VW[:, 0:64]
-            rc = dgemm(c, false, m - B, B, B, 1.0, Qb0 + (size_t)B * B, B, SM(SM_XM), B, 0.0, VW0 + (size_t)B * 2 * B, 2 * B);
-            if (rc) return rc;
-            copy_v_kernel<<<(unsigned)(((m - B) * B + 255) / 256), 256, 0, cs>>>(m, B, VW0, Vs, ld);
+            panel_gram_kernel<false><<<nb, 256, 2 * MAT * 8, st>>>(m, P, ld, nullptr, nullptr, parts);
+            sum_partials_kernel<<<B * B / 32, 256, 0, st>>>((int)nb, parts, SM(SM_G1));
+            chol_inv16_kernel<<<1, 256, CHOL16_LDS, st>>>(SM(SM_G1), SM(SM_R1), SM(SM_R1INV), w.fail);
+            panel_gram_kernel<true><<<nb, 256, 2 * MAT * 8, st>>>(m, P, ld, SM(SM_R1INV), Qb0, parts);
+            sum_partials_kernel<<<B * B / 32, 256, 0, st>>>((int)nb, parts, SM(SM_G2));
+            recon_kernel<<<1, 256, 3 * MAT * 8, st>>>(SM(SM_G2), SM(SM_R1), Qb0, P, ld, VW0, Vs, ld, Tp, SM(SM_XM), SM(SM_RPROD), w.fail);
+            panel_v_kernel<<<nb, 256, 3 * MAT * 8, st>>>(m, Qb0, SM(SM_XM), VW0, Vs, ld, VWt + 128, ldt);
         } else {
-            small_qr_kernel<<<1, 256, LDS4, cs>>>((int)m, P, ld, VW0, Vs, ld, Tp);
+            small_qr_kernel<<<1, 256, LDS4, st>>>((int)m, P, ld, VW0, Vs, ld, Tp);
         }
         PG_HIP(hipGetLastError());
         return PG_OK;
     };
-    // Look-ahead (opt-in: PG_SB2_LOOKAHEAD=<CUs to reserve>): the rank-128 update of panel j is issued as its first tile column (which
-    // holds the next panel) and the rest; the rest runs on a second stream whose CU mask leaves some CUs out, the next panel's
-    // factorisation — a chain of single-workgroup kernels and small GEMMs, ~300 us of mostly idle chip — follows the first tile column
-    // on the caller's stream.  [V W] is read by the update from its transposed copy, so the factorisation may overwrite V, Q and the
-    // small matrices at once.  (First version: the factorisation on a high-priority stream beside an unmasked update.  The two did
-    // run side by side, but the chain's single wavefronts shared SIMDs with the update's MFMA waves and slowed down by what they hid:
-    // Cholesky 61 -> 145 us, reconstruction 182 -> 205 us, phase 116 ms against 118.7.)
-    pg_ctx side = *ctx;
-    side.scratch = nullptr; side.scratch_bytes = 0; side.stream = nullptr;
-    hipEvent_t e_col = nullptr, e_fac = nullptr;
-    bool ahead = false;
-    if (const char *e_ = getenv("PG_SB2_LOOKAHEAD")) {
-        const int req = atoi(e_);
-        bool ok;
-        if (req == -2) {       // -2: a second stream of the LOWEST priority: the update's workgroups yield freed slots to the panel kernels
-            int least = 0, greatest = 0;
-            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            ok = hipStreamCreateWithPriority(&side.stream, hipStreamNonBlocking, least) == hipSuccess;
-        } else if (req < 0) ok = hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking) == hipSuccess;       // -1: a plain second stream
-        else {
-            const int reserve = std::max(1, std::min(req, ctx->num_cu / 2));
-            uint32_t mask[16];
-            const int words = (ctx->num_cu + 31) / 32;
-            for (int q = 0; q < 16; q++) mask[q] = 0;
-            for (int c = reserve; c < ctx->num_cu; c++) mask[c / 32] |= 1u << (c % 32);
-            ok = words <= 16 && hipExtStreamCreateWithCUMask(&side.stream, (uint32_t)words, mask) == hipSuccess;
-        }
-        ahead = req != 0 && ok && hipEventCreateWithFlags(&e_col, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&e_fac, hipEventDisableTiming) == hipSuccess;
-        if (!ahead) (void)hipGetLastError();
-    }
-    auto finish = [&](int rc) {
-        if (side.stream) { (void)hipStreamSynchronize(side.stream); (void)hipStreamDestroy(side.stream); }
-        if (e_col) (void)hipEventDestroy(e_col);
-        if (e_fac) (void)hipEventDestroy(e_fac);
-        if (side.scratch) (void)hipFree(side.scratch);
-        return rc;
-    };
     int pan = 0;
-    bool factored = false;          // the current panel's factorisation has been issued (by the previous iteration's look-ahead)
     for (int j = 0; n - j - B >= 2; j += B, pan++) {
         const long long m = n - j - B;
         double *Tp = w.Tst + (size_t)pan * B * B;
-        int rc = PG_OK;
-        if (!factored) rc = factor(ctx, j, pan);
-        else if (hipStreamWaitEvent(st, e_fac, 0) != hipSuccess) rc = PG_EHIP;
-        if (rc) return finish(rc);
+        int rc = factor(j, pan);
+        if (rc) return rc;
         // two-sided update of A22 = A[j+64:, j+64:] (m x m):  Y = A22 V T,  W = Y - 1/2 V (T' (V' Y)),  A22 -= V W' + W V'
         const long long off = j + B, off_al = off & ~(long long)127, pad = off - off_al;      // pad = 0 or 64
         double *A22al = A + (size_t)off_al * ld + off_al;
         double *V = VW0, *Wc = VW0 + B;                           // columns 0..63 / 64..127 of VW (ld 128)
-        double *const VWt = VWt_of(pan);
         DgemmDesc::Partials xp;
         {   // X = A22 V: A22 symmetric with its lower triangle (+ diagonal tiles) valid
             DgemmDesc d;
             d.symA = true; d.M = m + pad; d.N = B; d.K = m + pad; d.alpha = 1.0; d.beta = 0.0;
             d.A = A22al; d.lda = ld; d.B = VW0 - (size_t)pad * 2 * B; d.ldb = 2 * B; d.C = Qb0 - (size_t)pad * B; d.ldc = B;
-            if (fused && m > B) d.partials = &xp;            // the slices of a split K are summed by the kernel that consumes X
+            if (m > B) d.partials = &xp;            // the slices of a split K are summed by the kernel that consumes X
             rc = dgemm_ex(ctx, d);
         }
-        if (fused && m > B) {
-            if (rc) return finish(rc);
+        if (m > B) {
+            if (rc) return rc;
             const unsigned nb = (unsigned)((m + B - 1) / B);
             const double *slabs = (xp.slices > 1) ? xp.ws : Qb0 - (size_t)pad * B;
             panel_xy_kernel<<<nb, 256, 3 * MAT * 8, st>>>(m, pad, xp.slices, slabs, (m + pad) * B, Tp, VW0, parts);      // Y = X T, partials of V'Y
             sum_partials_kernel<<<B * B / 32, 256, 0, st>>>((int)nb, parts, SM(SM_M1));
             panel_w_kernel<<<nb, 256, 3 * MAT * 8, st>>>(m, Tp, SM(SM_M1), VW0, VWt + 128, ldt);                            // W = Y - 1/2 V T'(V'Y)
-            if (hipGetLastError() != hipSuccess) return finish(PG_EHIP);
-        } else {
+            if (hipGetLastError() != hipSuccess) return PG_EHIP;
+        } else {          // the last panel (small_qr_kernel): thin products as GEMM launches
             if (!rc) rc = dgemm(ctx, false, m, B, B, 1.0, Qb0, B, Tp, B, 0.0, Wc, 2 * B);               // Y  = X T           -> W columns
             if (!rc) rc = dgemm(ctx, true, B, B, m, 1.0, V, 2 * B, Wc, 2 * B, 0.0, SM(SM_M1), B);       // M1 = V' Y
             if (!rc) rc = dgemm(ctx, true, B, B, B, -0.5, Tp, B, SM(SM_M1), B, 0.0, SM(SM_M2), B);      // M2 = -1/2 T' M1
             if (!rc) rc = dgemm(ctx, false, m, B, B, 1.0, V, 2 * B, SM(SM_M2), B, 1.0, Wc, 2 * B);      // W  = Y + V M2
-            if (rc) return finish(rc);
+            if (rc) return rc;
             transpose_vw_kernel<<<dim3((unsigned)((m + 63) / 64), 2), 256, 0, st>>>(m, VW0, VWt + 128, ldt);
-            if (hipGetLastError() != hipSuccess) return finish(PG_EHIP);
+            if (hipGetLastError() != hipSuccess) return PG_EHIP;
         }
-        // A22 -= [V W] [W V]' on the lower triangle: first tile column, then (beside the next panel's factorisation) the rest
+        // A22 -= [V W] [W V]' on the lower triangle
         const long long mm = m + pad;
-        const bool next = n - (j + B) - B >= 2;
         DgemmDesc d;
         d.transA = true; d.kxorB = B; d.K = 2 * B; d.alpha = -1.0; d.beta = 1.0; d.lower_only = true; d.lda = ldt; d.ldb = ldt; d.ldc = ld;
-        const bool split = ahead && next && mm > 128 && m > B;
-        factored = false;
-        if (split && fused) {
-            // Look-ahead (r4).  The next panel is the trailing matrix's first 64 columns: they are updated first, by a thin kernel of its
-            // own (6 us; the first 128-column tile column as a GEMM launch took 54: ~60 tiles on 256 CUs), the next factorisation follows
-            // on this stream; everything else of the update goes to the second stream: the other half of tile column 0 (aligned columns
-            // 64..127; only when the trailing matrix starts on a tile boundary — otherwise that tile column is the 64 zero columns in front
-            // and the next panel, nothing more) as a 64-wide strip, and the lower triangle of the tiles from (1, 1) on.
-            if (hipEventRecord(e_col, st) != hipSuccess) return finish(PG_EHIP);
-            if (hipStreamWaitEvent(side.stream, e_col, 0) != hipSuccess) return finish(PG_EHIP);
-            if (pad == 0) {
-                DgemmDesc s_ = d;
-                s_.lower_only = false; s_.M = mm; s_.N = B;
-                s_.A = VWt + 128; s_.B = VWt + 128 + B; s_.C = A22al + B;
-                rc = dgemm_ex(&side, s_);
-                if (rc) return finish(rc);
-            }
-            d.M = mm - 128; d.N = mm - 128;
-            d.A = VWt + 128 - pad + 128; d.B = d.A; d.C = A22al + (size_t)128 * ld + 128;
-            rc = dgemm_ex(&side, d);
-            if (rc) return finish(rc);
-            if (hipEventRecord(e_fac, side.stream) != hipSuccess) return finish(PG_EHIP);
-            panel_next_update_kernel<<<(unsigned)((m + B - 1) / B), 256, 4 * MAT * 8, st>>>(m, VW0, A + (size_t)off * ld + off, ld);
-            if (hipGetLastError() != hipSuccess) return finish(PG_EHIP);
-            rc = factor(ctx, j + B, pan + 1);
-            if (rc) return finish(rc);
-            factored = true;
-            continue;
-        }
-        if (split) {
-            // the part of the update beyond the first tile column: on the masked stream, as soon as [V W]' is there
-            if (hipEventRecord(e_col, st) != hipSuccess) return finish(PG_EHIP);
-            if (hipStreamWaitEvent(side.stream, e_col, 0) != hipSuccess) return finish(PG_EHIP);
-            d.M = mm - 128; d.N = mm - 128;
-            d.A = VWt + 128 - pad + 128; d.B = d.A; d.C = A22al + (size_t)128 * ld + 128;
-            rc = dgemm_ex(&side, d);
-            if (rc) return finish(rc);
-            if (hipEventRecord(e_fac, side.stream) != hipSuccess) return finish(PG_EHIP);
-        }
-        d.M = mm; d.N = split ? 128 : mm;
+        d.M = mm; d.N = mm;
         d.A = VWt + 128 - pad; d.B = d.A; d.C = A22al;
         rc = dgemm_ex(ctx, d);
-        if (rc) return finish(rc);
-        if (split) {
-            // the next panel's factorisation behind the first tile column, beside the rest
-            rc = factor(ctx, j + B, pan + 1);
-            if (rc) return finish(rc);
-            factored = true;
-        }
+        if (rc) return rc;
     }
-    if (factored && hipStreamWaitEvent(st, e_fac, 0) != hipSuccess) return finish(PG_EHIP);
-    return finish(PG_OK);
+    return PG_OK;
 }
 
 // ---- band storage ---------------------------------------------------------------------------------------------------------------
@@ -1778,13 +1571,6 @@ int sb2st_device(pg_ctx *ctx, int n, const double *A, double *d, double *e, Sb2W
         if (stationary) {
             PG_HIP(hipMemsetAsync(w.mail, 0, (size_t)nblk * MB_LD * 8, st));
             const int test_fault = (getenv("PG_BC_TEST_FAULT") && atoi(getenv("PG_BC_TEST_FAULT")) != 0) ? 1 : 0;
-            const int exp_waves = getenv("PG_BC_STAT_WAVES") ? atoi(getenv("PG_BC_STAT_WAVES")) : 0;      // A/B: wavefronts per workgroup of the one-per-CU form
-            if (per_cu == 1 && exp_waves == 8) bc_stationary_kernel<8><<<nblk, 64 * 8, BC_LDS8, st>>>(n, w.S, w.VV, w.TAU, w.nk, w.mail, nblk, w.prog + n, w.fail, test_fault);
-            else if (per_cu == 1 && exp_waves == 4) {
-                constexpr int BC_LDS4 = (B * WP + 4 * B + 2 * 4 * B + 4) * 8;
-                PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bc_stationary_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, BC_LDS4));
-                bc_stationary_kernel<4><<<nblk, 64 * 4, BC_LDS4, st>>>(n, w.S, w.VV, w.TAU, w.nk, w.mail, nblk, w.prog + n, w.fail, test_fault);
-            } else
             if (per_cu == 1) bc_stationary_kernel<NW><<<nblk, 64 * NW, BC_LDS, st>>>(n, w.S, w.VV, w.TAU, w.nk, w.mail, nblk, w.prog + n, w.fail, test_fault);
             else bc_stationary_kernel<8><<<nblk, 64 * 8, BC_LDS8, st>>>(n, w.S, w.VV, w.TAU, w.nk, w.mail, nblk, w.prog + n, w.fail, test_fault);
         } else {
@@ -1875,7 +1661,7 @@ __global__ __launch_bounds__(256) void bt2_prep_kernel(int n, int nk, int ng, co
     }
 }
 
-// One reflector block applied to one slab of 64 columns of Z in ONE pass:  Zs <- Zs - (V T) (V' Zs).
+// One reflector block applied to one slab of 64 columns of Z in ONE pass:  Zs <- Zs - (V T) (V' Zs)  (`apply` in bt2_apply4_kernel).
 // The slab (127 rows x 64 columns) is read from HBM once, into REGISTERS, in the accumulator layout of the fp64 MFMA (a 16 x 16 tile:
 // lane l, component e = row (l >> 4) + 4 e, column l & 15) — which is also the layout of its B operand for the four k-steps of a
 // 16-row tile, so W = V' Zs needs no LDS copy of the slab, and the same registers are the C operand of the second product.
@@ -1890,181 +1676,10 @@ constexpr int BT2_ZP = BT2_NS + 16;        // LDS pitch of W: consecutive k-rows
 constexpr int BT2_AP = 128 + 16;           // pitch of a staged operand chunk [CK][128]
 constexpr int BT2_CK = 16;                 // k-rows per staged operand chunk
 constexpr int BT2_LDS_BYTES = (64 * BT2_ZP + 2 * BT2_CK * BT2_AP) * 8;
-struct Bt2Args {
-    int n, nb;
-    long long row_first, h_last;
-    const double *Vp, *Vtp;       // block of batch element 0
-    long long blk_stride;         // elements between consecutive batch elements
-    double *Z;
-    int vec;                      // rows of Z are 16-byte aligned (n even)
-};
-__global__ __launch_bounds__(256, 2) void bt2_apply_kernel(Bt2Args ar)
-{
-    extern __shared__ double lds[];
-    double *Ws = lds;                               // [64][ZP]    Ws[sweep][c]
-    double *As = Ws + 64 * BT2_ZP;                  // [2][CK][AP] operand chunk, k-major
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int z = blockIdx.y, n = ar.n;
-    const long long row0 = ar.row_first + (long long)z * (B + SB_G);
-    const int h = (z == ar.nb - 1) ? (int)ar.h_last : B + SB_G - 1;
-    const int c0 = blockIdx.x * BT2_NS, ncols = (n - c0 < BT2_NS) ? n - c0 : BT2_NS;
-    const double *V = ar.Vp + (long long)z * ar.blk_stride, *Vt = ar.Vtp + (long long)z * ar.blk_stride;
-    double *Zg = ar.Z + (size_t)row0 * n + c0;
-    constexpr int CK = BT2_CK, NA = 128 / CK, NB2 = SB_G / CK;
-    // ---- slab in.  Wavefront w owns column tile w (columns 16 w .. 16 w + 15) of the slab, all 128 rows, from here to the end:
-    // B operand of the first product, C operand and result of the second.  Full, 16-byte-aligned slabs come in whole rows (512
-    // contiguous bytes, 16 per lane) through the operand staging space, 32 rows at a time, and are picked up from LDS in the
-    // accumulator layout; lane-wise 8-byte loads in that layout were the slow part of the kernel (dgemm's epilogue had the same
-    // disease).  Edge slabs (last columns, odd n) keep the element-wise path.
-    doublex4 zr[8];
-    const int rsub = lane >> 4, csub = lane & 15;
-    const int colw = wave * 16 + csub;              // this lane's column of the slab
-    const bool vec = ar.vec && ncols == BT2_NS;
-    constexpr int SP2 = BT2_NS + 8;                 // pitch of a staged slab row
-    if (vec) {
-        double2 cv[4][4];           // all 16 loads of the thread in flight at once: the memory latency is paid once per slab, not per chunk
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++)
-#pragma unroll
-            for (int ps = 0; ps < 4; ps++) {
-                const int row = 32 * ch + 8 * ps + (tid >> 5);
-                cv[ch][ps] = (row < h) ? *reinterpret_cast<const double2 *>(Zg + (size_t)row * n + 2 * (tid & 31)) : make_double2(0.0, 0.0);
-            }
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++) {
-#pragma unroll
-            for (int ps = 0; ps < 4; ps++) *reinterpret_cast<double2 *>(As + (8 * ps + (tid >> 5)) * SP2 + 2 * (tid & 31)) = cv[ch][ps];
-            __syncthreads();
-#pragma unroll
-            for (int tt = 0; tt < 2; tt++)
-#pragma unroll
-                for (int e = 0; e < 4; e++) zr[2 * ch + tt][e] = As[(16 * tt + rsub + 4 * e) * SP2 + colw];
-            __syncthreads();
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < 8; t++)
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int row = t * 16 + rsub + 4 * e;
-                zr[t][e] = (row < h && colw < ncols) ? Zg[(size_t)row * n + colw] : 0.0;
-            }
-    }
-    // ---- phase A: W (64 sweeps x 64 columns) = V' Zs, K = 128 rows; operand chunk = CK rows of V (contiguous doubles).
-    // Sweep tile I of V' is non-zero on the rows 16 I .. 16 I + 78 only (column i of V: rows i .. i + 63): row tiles I .. I + 4 of
-    // the eight — 20 tile products of 32; the others would add exact zeros.
-    doublex4 accA[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int e = 0; e < 4; e++) accA[i][e] = 0.0;
-    double2 stg[CK / 8];
-    auto gloadA = [&](int kt) {      // chunk kt: rows CK kt ..: CK * 64 contiguous doubles; thread -> double2 number tid (+ 256 per pass)
-#pragma unroll
-        for (int ps = 0; ps < CK / 8; ps++) stg[ps] = *reinterpret_cast<const double2 *>(V + (size_t)kt * CK * SB_G + 2 * (ps * 256 + tid));
-    };
-    auto lstoreA = [&](int buf) {
-#pragma unroll
-        for (int ps = 0; ps < CK / 8; ps++) {
-            const int e0 = 2 * (ps * 256 + tid);           // element of the chunk: row e0 / 64, sweep e0 % 64
-            double *d = As + (buf * CK + (e0 >> 6)) * BT2_AP + (e0 & 63);
-            d[0] = stg[ps].x; d[1] = stg[ps].y;
-        }
-    };
-    static_assert(BT2_CK == 16, "the zero pattern below is per row tile of 16");
-    gloadA(0);
-    lstoreA(0);
-    __syncthreads();
-#pragma unroll
-    for (int kt = 0; kt < NA; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < NA) gloadA(kt + 1);
-#pragma unroll
-        for (int kk = 0; kk < CK; kk += 4) {
-            const int kr = kk + rsub;
-#pragma unroll
-            for (int I = 0; I < 4; I++) {
-                if (kt < I || kt > I + 4) continue;
-                accA[I] = __builtin_amdgcn_mfma_f64_16x16x4f64(As[(buf * CK + kr) * BT2_AP + I * 16 + csub], zr[kt][kk / 4], accA[I], 0, 0, 0);
-            }
-        }
-        if (kt + 1 < NA) lstoreA(buf ^ 1);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int I = 0; I < 4; I++)
-#pragma unroll
-        for (int e = 0; e < 4; e++) Ws[(I * 16 + rsub + 4 * e) * BT2_ZP + colw] = accA[I][e];
-    // ---- phase B: Zs (128 x 64) -= (V T) W, K = 64 sweeps, accumulated onto the slab registers themselves (V T enters negated);
-    // operand chunk = CK sweeps of all 128 rows of V T (row-major [row][sweep]).  Row tile R of V T is non-zero from sweep 16 R - 63
-    // on, i.e. on the sweep tiles max(0, R - 4) .. 3: 26 tile products of 32.
-    double rt[CK / 8][4];
-    auto gloadB = [&](int kt) {      // thread -> row tid / 2, 4 consecutive sweeps (+ 8 per pass)
-#pragma unroll
-        for (int ps = 0; ps < CK / 8; ps++) {
-            const double *src = Vt + (size_t)(tid >> 1) * SB_G + kt * CK + ps * 8 + (tid & 1) * 4;
-            const double2 a = *reinterpret_cast<const double2 *>(src), b2 = *reinterpret_cast<const double2 *>(src + 2);
-            rt[ps][0] = a.x; rt[ps][1] = a.y; rt[ps][2] = b2.x; rt[ps][3] = b2.y;
-        }
-    };
-    auto lstoreB = [&](int buf) {
-#pragma unroll
-        for (int ps = 0; ps < CK / 8; ps++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) As[(buf * CK + ps * 8 + (tid & 1) * 4 + q) * BT2_AP + (tid >> 1)] = rt[ps][q];
-    };
-    gloadB(0);
-    lstoreB(0);
-    __syncthreads();          // also: W complete in LDS
-#pragma unroll
-    for (int kt = 0; kt < NB2; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < NB2) gloadB(kt + 1);
-#pragma unroll
-        for (int kk = 0; kk < CK; kk += 4) {
-            const int kr = kk + rsub;
-            const double b2 = Ws[(kt * CK + kr) * BT2_ZP + colw];
-#pragma unroll
-            for (int R = 0; R < 8; R++) {
-                if (kt < R - 4) continue;
-                zr[R] = __builtin_amdgcn_mfma_f64_16x16x4f64(-As[(buf * CK + kr) * BT2_AP + R * 16 + csub], b2, zr[R], 0, 0, 0);
-            }
-        }
-        if (kt + 1 < NB2) lstoreB(buf ^ 1);
-        __syncthreads();
-    }
-    // ---- slab out
-    if (vec) {
-        // chunk ch = rows 32 ch ..: into the staging space, then everybody stores whole rows
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++) {
-#pragma unroll
-            for (int tt = 0; tt < 2; tt++)
-#pragma unroll
-                for (int e = 0; e < 4; e++) As[(16 * tt + rsub + 4 * e) * SP2 + colw] = zr[2 * ch + tt][e];
-            __syncthreads();
-#pragma unroll
-            for (int ps = 0; ps < 4; ps++) {
-                const int row = 32 * ch + 8 * ps + (tid >> 5);
-                if (row < h)
-                    *reinterpret_cast<double2 *>(Zg + (size_t)row * n + 2 * (tid & 31)) = *reinterpret_cast<const double2 *>(As + (8 * ps + (tid >> 5)) * SP2 + 2 * (tid & 31));
-            }
-            __syncthreads();
-        }
-    } else {
-#pragma unroll
-        for (int R = 0; R < 8; R++)
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int row = R * 16 + rsub + 4 * e;
-                if (row < h && colw < ncols) Zg[(size_t)row * n + colw] = zr[R][e];
-            }
-    }
-}
 
 // ---- four reflector blocks per pass ------------------------------------------------------------------------------------------------
-// bt2_apply_kernel moves a slab of Z through HBM once per block: 157 x (read + write) of Z at n = 10 000, 250 GB, and that — not
-// the MFMA work — sets its time.  Blocks (G, k), (G, k + 1), (G - 1, k), (G - 1, k + 1) lie on 255 consecutive rows (each block 127 rows,
+// A kernel that applies one block per launch moves a slab of Z through HBM once per block: 157 x (read + write) of Z at n = 10 000,
+// 250 GB, and that — not the MFMA work — sets its time.  Blocks (G, k), (G, k + 1), (G - 1, k), (G - 1, k + 1) lie on 255 consecutive rows (each block 127 rows,
 // starting 64 apart) and may be applied in exactly that order, so a workgroup that keeps 256 rows x 64 columns in registers applies all
 // four on ONE trip of the slab: half the traffic, a quarter of the launches' slab latencies.  The 2 x 2 super-blocks (u, ks) — groups
 // glast - 2u and glast - 2u - 1, block indices 2 ks and 2 ks + 1 — depend on each other exactly like the blocks do, so they run on
@@ -2139,7 +1754,7 @@ __global__ __launch_bounds__(256, 2) void bt2_apply4_kernel(Bt2SArgs ar)
                 zr[t][e] = (row_ok(row) && colw < ncols) ? Zg[(size_t)(slab0 + row) * n + colw] : 0.0;
             }
     }
-    // one block on the row tiles T0 .. T0 + 7 of the slab registers (the body of bt2_apply_kernel).  Operand chunks are fetched TWO
+    // one block on the row tiles T0 .. T0 + 7 of the slab registers (the one-block scheme above).  Operand chunks are fetched TWO
     // steps ahead (a step is 8 - 16 MFMAs, 0.2 - 0.4 us: less than an L2 round trip), the first two chunks of the second product
     // during the last two steps of the first.
     // The first two chunks of the NEXT block are asked for during the last two steps of the current one (the staging registers of the first
@@ -2284,7 +1899,6 @@ int bt2_prep_device(pg_ctx *ctx, int n, Sb2Work &w, hipStream_t st)
     const size_t lds = (size_t)(VR * P65 + 2 * MAT) * 8;
     // per device, on every call (see sy2sb_device)
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bt2_prep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bt2_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BT2_LDS_BYTES));
     PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bt2_apply4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BT2_LDS_BYTES));
     bt2_prep_kernel<<<dim3(w.ng, w.kmax), 256, lds, st>>>(n, w.nk, w.ng, w.VV, w.TAU, w.Vp, w.Vtp);
     PG_HIP(hipGetLastError());
@@ -2295,46 +1909,16 @@ int bt2_device(pg_ctx *ctx, int n, double *Z, Sb2Work &w, bool prepared)
 {
     if (n < 3) return PG_OK;
     hipStream_t st = ctx->stream;
-    constexpr int VR = 128, HGT = B + SB_G - 1;      // rows of a block
     const int ng = w.ng;
     if (!prepared) { const int rc = bt2_prep_device(ctx, n, w, st); if (rc) return rc; }
-    const size_t blk = (size_t)VR * SB_G;
-    const int glast = ng - 1;
     const int nslab = (n + BT2_NS - 1) / BT2_NS;
-    bool four = true;       // four blocks per trip of a slab (bt2_apply4_kernel); PG_BT2_FOUR=0: one block per trip
-    if (const char *e_ = getenv("PG_BT2_FOUR")) four = atoi(e_) != 0;
-    if (four) {
-        const int nu = (ng + 1) / 2, kcount = (n - 1 + B - 1) / B, nks = (kcount + 1) / 2;
-        const int lds_pad = getenv("PG_BT2_LDS_PAD") ? atoi(getenv("PG_BT2_LDS_PAD")) : 0;      // A/B: > 6 KB leaves room for ONE workgroup per CU only
-        if (lds_pad > 0) PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bt2_apply4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BT2_LDS_BYTES + lds_pad));
-        for (int ts = 0; ts <= (nu - 1) + (nks - 1); ts++) {
-            const int u_lo = std::max(0, ts - (nks - 1)), u_hi = std::min(ts, nu - 1);
-            Bt2SArgs ar;
-            ar.n = n; ar.ng = ng; ar.ts = ts; ar.u_first = u_lo; ar.Vp = w.Vp; ar.Vtp = w.Vtp; ar.Z = Z;
-            ar.vec = ((n & 1) == 0 && (uintptr_t)Z % 16 == 0) ? 1 : 0;
-            if (const char *e_ = getenv("PG_BT2_VEC")) ar.vec = ar.vec && atoi(e_) != 0;      // A/B: 0 = the slab straight between memory and the MFMA layout
-            bt2_apply4_kernel<<<dim3(nslab, u_hi - u_lo + 1), 256, BT2_LDS_BYTES + lds_pad, st>>>(ar);
-        }
-        PG_HIP(hipGetLastError());
-        return PG_OK;
-    }
-    // wavefront t: blocks (G, k) with (glast - G) + k = t; their rows start (g + b) apart
-    for (int t = 0;; t++) {
-        const int kmin = std::max(0, t - glast);
-        const long long base = (long long)SB_G * (glast - t) + 1;          // row0(k) = base + k (g + b)
-        // largest k with G = glast - t + k <= glast (k <= t) and row0 < n
-        long long kmx = t;
-        if (base + kmx * (SB_G + B) >= n) kmx = (n - 1 - base) / (SB_G + B);   // floor; base may be negative only when kmin > 0
-        if (n - 1 - base < 0) kmx = -1;
-        if (kmx < kmin) break;     // wavefronts are non-empty up to the last one (t <= glast: k = 0 exists; beyond: once empty, always empty)
-        const int nb = (int)(kmx - kmin + 1);
-        const long long row_first = base + (long long)kmin * (SB_G + B), row_last = base + kmx * (SB_G + B);
-        const int G0 = glast - t + kmin;
-        Bt2Args ar;
-        ar.n = n; ar.nb = nb; ar.row_first = row_first; ar.h_last = std::min<long long>(HGT, n - row_last);
-        ar.Vp = w.Vp + ((size_t)kmin * ng + G0) * blk; ar.Vtp = w.Vtp + ((size_t)kmin * ng + G0) * blk;
-        ar.blk_stride = (long long)(ng + 1) * blk; ar.Z = Z; ar.vec = ((n & 1) == 0 && (uintptr_t)Z % 16 == 0) ? 1 : 0;
-        bt2_apply_kernel<<<dim3(nslab, nb), 256, BT2_LDS_BYTES, st>>>(ar);
+    const int nu = (ng + 1) / 2, kcount = (n - 1 + B - 1) / B, nks = (kcount + 1) / 2;
+    for (int ts = 0; ts <= (nu - 1) + (nks - 1); ts++) {
+        const int u_lo = std::max(0, ts - (nks - 1)), u_hi = std::min(ts, nu - 1);
+        Bt2SArgs ar;
+        ar.n = n; ar.ng = ng; ar.ts = ts; ar.u_first = u_lo; ar.Vp = w.Vp; ar.Vtp = w.Vtp; ar.Z = Z;
+        ar.vec = ((n & 1) == 0 && (uintptr_t)Z % 16 == 0) ? 1 : 0;
+        bt2_apply4_kernel<<<dim3(nslab, u_hi - u_lo + 1), 256, BT2_LDS_BYTES, st>>>(ar);
     }
     PG_HIP(hipGetLastError());
     return PG_OK;

@@ -42,13 +42,12 @@ def _geno(rng, n, p, standardise):
 
 
 def _kernel_env(monkeypatch, kern):
-    """the three kernels a genotype block can take: int8 digit planes (shipped), fp16 x 2 on 16 x 16 x 32 (PG_GENO_I8=0: the kernel of
-    split-plane blocks, and the r2-r3 genotype kernel), its 32 x 32 x 16 instantiation (PG_GENO_MFMA=32: measured alternative, slower)"""
+    """the two kernels a genotype block can take: int8 digit planes (shipped), fp16 x 2 on 16 x 16 x 32 (PG_GENO_I8=0: the kernel of
+    split-plane blocks, and the r2-r3 genotype kernel)"""
     monkeypatch.setenv("PG_GENO_I8", "1" if kern == "i8" else "0")
-    monkeypatch.setenv("PG_GENO_MFMA", "32" if kern == "f16_32x32" else "16")
 
 
-@pytest.mark.parametrize("kern", ["i8", "f16", "f16_32x32"])
+@pytest.mark.parametrize("kern", ["i8", "f16"])
 @pytest.mark.parametrize("n,p,std", [(64, 32, True), (257, 130, True), (300, 128, False), (1000, 516, True), (2000, 200, True)])
 def test_rotate_genotype_fast_path(n, p, std, kern, ctx, monkeypatch):
     """genotype path: error vs the fp64 rotation within the fp32-GEMM class (and no worse than the fp32-MFMA path), on each of its kernels."""

@@ -42,7 +42,7 @@ def ctx():
 
 @pytest.fixture(autouse=True)
 def _shipped_path(monkeypatch):
-    for v in ("PG_GENO_I8", "PG_GENO_MFMA", "PG_GENO_ONEPASS", "PG_GENO_CHUNK_MB"):
+    for v in ("PG_GENO_I8", "PG_GENO_ONEPASS", "PG_GENO_CHUNK_MB"):
         monkeypatch.delenv(v, raising=False)
 
 
