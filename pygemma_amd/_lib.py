@@ -19,6 +19,10 @@ VC_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpygemma_vc.so")     # 
 VC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pygemma_vc.h")
 VC_SYMBOLS = []  # the functions VC_HEADER declares, in its order: filled by load_vc()
 _vc = None
+CC_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpygemma_cc.so")     # the case/control unit: a library of its own
+CC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pygemma_cc.h")
+CC_SYMBOLS = []  # the functions CC_HEADER declares, in its order: filled by load_cc()
+_cc = None
 SYMBOLS = []     # the functions HEADER declares, in its order: filled by load()
 _CTYPES = {"int": C.c_int, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
 
@@ -100,6 +104,27 @@ def load_vc():
     VC_SYMBOLS[:] = [fn for fn, _, _ in decls]
     _vc = V
     return V
+
+
+def load_cc():
+    """Load libpygemma_cc.so (csrc/case_control.hip: lmm.case_control's kernels) beside the main library, which it needs, and bind
+    it from include/pygemma_cc.h.  Called by lmm.case_control, not at import, as load_vc is."""
+    global _cc
+    if _cc is not None:
+        return _cc
+    load()
+    for path in (CC_LIB_PATH, CC_HEADER):
+        if not os.path.exists(path):
+            raise PgError(f"{path} not found: build the HIP extension (python -c 'import __graft_entry__ as g; g.build()')")
+    K = C.CDLL(CC_LIB_PATH)
+    with open(CC_HEADER) as hdr:
+        decls = parse_header(hdr.read())
+    for fn, restype, argtypes in decls:
+        f = getattr(K, fn)
+        f.restype, f.argtypes = restype, argtypes
+    CC_SYMBOLS[:] = [fn for fn, _, _ in decls]
+    _cc = K
+    return K
 
 
 def check(rc, what=""):

@@ -43,7 +43,7 @@ from . import model as _model
 from .vc import RemlResult, reml, vc_kinship     # noqa: F401  (re-exported: variance components for several kinship matrices)
 
 __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
-           "kinship", "ld", "ld_window", "ld_prune", "clump", "ld_scores", "ldsc", "LdscResult", "epistasis", "EpistasisResult", "prs", "prs_weights", "king", "ibs",
+           "kinship", "ld", "ld_window", "ld_prune", "clump", "ld_scores", "ldsc", "LdscResult", "epistasis", "EpistasisResult", "case_control", "prs", "prs_weights", "king", "ibs",
            "sample_stats", "related_pairs", "unrelated", "pca", "pca_project", "PcaResult", "reml", "vc_kinship", "RemlResult"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
@@ -1432,6 +1432,147 @@ def epistasis(X, y, *, a=None, b=None, p=_EPI_P, chi2=None, case_only=False, snp
                       "bytes_in": sum(s.p * s.row_bytes for s in srcs), "seconds": time.time() - t0})
     _log(verbose, f"epistasis: {na} x {nb} SNPs with {n} individuals, {len(pairs)} pairs at chi2 >= {chi2_min:.3f} in {time.time() - t0:.3f} s")
     return EpistasisResult(pairs, summary, chi2_min)
+
+
+# ---- per-SNP case/control tests on contingency tables (csrc/case_control.hip) ---------------------------------------------------
+_CC_MAX_STRATA = 16            # PG_CC_MAX_STRATA
+_CC_COUNTS = ("case0", "case1", "case2", "case_miss", "ctrl0", "ctrl1", "ctrl2", "ctrl_miss")
+_CC_STAT = ("af_case", "af_ctrl", "or", "chi2_allelic", "chi2_trend", "chi2_geno", "chi2_dom", "chi2_rec", "p_fisher", "chi2_cmh", "or_mh")   # stat's columns
+_CC_COLS = _CC_COUNTS + ("hard", "af_case", "af_ctrl", "or", "chi2_allelic", "p_allelic", "chi2_trend", "p_trend", "chi2_geno", "p_geno", "chi2_dom",
+                         "p_dom", "chi2_rec", "p_rec", "p_fisher", "cmh_u", "cmh_v", "chi2_cmh", "p_cmh", "or_mh")
+_CC_CMH = ("cmh_u", "cmh_v", "chi2_cmh", "p_cmh", "or_mh")
+
+
+def _cc_p1(chi2):
+    """The upper tail of chi2 on 1 df, erfc(sqrt(chi2 / 2)), in one vectorised call; NaN stays NaN."""
+    from scipy import special as _spc      # lazily, as pygemma_lm does
+    return _spc.erfc(np.sqrt(np.asarray(chi2, np.float64) / 2.0))
+
+
+def _cc_p2(chi2):
+    """The upper tail of chi2 on 2 df, exp(-chi2 / 2); NaN stays NaN."""
+    return np.exp(-np.asarray(chi2, np.float64) / 2.0)
+
+
+def _cc_strata(strata, n):
+    """(int32 stratum of every sample in 0..S-1, -1 excluded; S) from integer labels or a pandas categorical: the labels in sorted order,
+    NaN and negative labels excluded.  (None, 1) without strata."""
+    if strata is None:
+        return None, 1
+    if isinstance(strata, pd.Categorical) or isinstance(getattr(strata, "dtype", None), pd.CategoricalDtype):
+        lab = np.asarray(pd.Categorical(strata).codes, np.float64)             # -1 where the label is missing
+    else:
+        lab = np.asarray(strata)
+        if lab.dtype.kind not in "biuf":
+            raise ValueError(f"strata must hold integer labels (or be a pandas categorical), not dtype {lab.dtype}")
+        lab = lab.astype(np.float64)
+    if lab.ndim != 1 or lab.shape[0] != n:
+        raise ValueError(f"shape mismatch: strata has shape {lab.shape} for {n} samples")
+    keep = np.isfinite(lab) & (lab >= 0)
+    if np.isinf(lab).any() or (lab[keep] != np.floor(lab[keep])).any():
+        raise ValueError("strata must hold integer labels; NaN or a negative label excludes the sample")
+    levels = np.unique(lab[keep])
+    if len(levels) < 1:
+        raise ValueError("strata leaves no sample in a stratum")
+    if len(levels) > _CC_MAX_STRATA:
+        raise ValueError(f"case_control takes at most {_CC_MAX_STRATA} strata, strata holds {len(levels)} labels")
+    code = np.full(n, -1, np.int32)
+    code[keep] = np.searchsorted(levels, lab[keep])
+    return code, len(levels)
+
+
+def case_control(X, y, *, strata=None, fisher=True, snps=None, device=0, snp_batch=None, verbose=0, stats=None):
+    """Per-SNP tests of a case/control trait on contingency tables: what PLINK prints with --assoc, --model, --fisher and --mh, every
+    statistic a function of exact integer counts that a popcount kernel reads from packed .bed words (csrc/case_control.hip).
+
+    X (n, p): whatever snp_stats takes — a PackedBed (honouring count_A1), or an int8, uint8, float32 or float64 array in C or Fortran
+    order, pinned or pageable — streamed in SNP batches of `snp_batch` columns through the two-slot feed; an array batch is packed into
+    2-bit records on the device first.  The results stay on the device until one download at the end and do not depend on the batch
+    boundaries.  .bed code 01, NaN and +-Inf are missing.  Only a hard-call SNP is tested (every observed value exactly 0, 1 or 2, as
+    for `ld`): any other SNP has `hard` False, counts 0 and NaN statistics.
+    y (n,): 1 case, 0 control (bool allowed), NaN excluded.  strata: None, or (n,) integer labels or a pandas categorical, mapped to
+    0..S-1 in sorted order, S <= 16; a sample with a NaN or negative stratum is excluded.
+    With r_i, s_i the cases and controls of genotype i among the called samples that have a status and a stratum, n_i = r_i + s_i,
+    R = sum r_i, S' = sum s_i, N = R + S', and per group A = n1 + 2 n2 alleles of the counted allele and 2 (group size) - A of the other,
+    the frame has p rows:
+      case0, case1, case2, case_miss, ctrl0, ctrl1, ctrl2, ctrl_miss (int64)   the 2 x 4 table, pooled over the strata
+      hard                           the SNP is hard-call
+      af_case, af_ctrl               A / (2 group size)
+      or                             a d / (b c) of the allelic 2 x 2 table; +inf when b c = 0 < a d, NaN when both are 0
+      chi2_allelic, p_allelic        1 df on the allelic table (--assoc)
+      chi2_trend, p_trend            Cochran-Armitage, weights 0, 1, 2, 1 df
+      chi2_geno, p_geno              2 df on the 2 x 3 table; NaN when a genotype is unseen
+      chi2_dom, p_dom, chi2_rec, p_rec   1 df: 1 + 2 against 0, and 2 against 0 + 1
+      p_fisher                       the two-sided exact test on the allelic table; absent with fisher=False
+      cmh_u, cmh_v, chi2_cmh, p_cmh, or_mh   Cochran-Mantel-Haenszel over the strata's allelic tables, no continuity correction:
+                                     u = sum a_k - row1_k col1_k / T_k, v = sum row1 row2 col1 col2 / (T^2 (T - 1)), chi2 = u^2 / v (NaN
+                                     when v = 0), or_mh = sum (a d / T) / sum (b c / T) (NaN when the divisor is 0), over the strata that
+                                     hold a called case and a called control; absent with strata=None
+      SNPs                           `snps`, when given
+    A 2 x 2 chi2 is NaN when a margin is 0; every statistic of a row is NaN when R = 0 or S' = 0 (the counts are still reported).
+    p-values on the host from the chi2 columns: erfc(sqrt(chi2 / 2)) on 1 df, exp(-chi2 / 2) on 2.
+    `stats` receives batches, bytes_in, seconds and lambda_gc = median(chi2_trend over its non-NaN rows) / chi2.ppf(0.5, 1).  Refused
+    with ValueError before any device work: X not 2-D or of another dtype, an empty X, y of another length or with values other than
+    0, 1, NaN, no case, no control, strata of another length, not integer or with more than 16 labels, `snps` of another length, a bad
+    snp_batch."""
+    _check_snp_batch(snp_batch)
+    X = _genotypes(X, "case_control")
+    n, p = X.shape
+    if n < 1 or p < 1:
+        raise ValueError(f"case_control needs at least one sample and one SNP: X holds n={n}, p={p}")
+    if snps is not None and len(snps) != p:
+        raise ValueError(f"shape mismatch: {len(snps)} SNP names for {p} SNPs")
+    group = _epi_group(y, n, False)
+    strat, S = _cc_strata(strata, n)
+    cnt, cmh, st, hard = _cc_stream(X, group, strat, S, bool(fisher), device, snp_batch, verbose, stats)
+    out = {col: cnt[:, k] for k, col in enumerate(_CC_COUNTS)}
+    out["hard"] = hard
+    out.update({col: st[:, k] for k, col in enumerate(_CC_STAT)})
+    out["cmh_u"], out["cmh_v"] = cmh[:, 0], cmh[:, 1]
+    for name in ("allelic", "trend", "dom", "rec", "cmh"):
+        out["p_" + name] = _cc_p1(out["chi2_" + name])
+    out["p_geno"] = _cc_p2(out["chi2_geno"])
+    drop = (() if fisher else ("p_fisher",)) + (_CC_CMH if strata is None else ())
+    if stats is not None:
+        z = out["chi2_trend"][~np.isnan(out["chi2_trend"])]
+        stats["lambda_gc"] = float(np.median(z) / _CHI2_MEDIAN) if z.size else float("nan")
+    return _frame(out, [col for col in _CC_COLS if col not in drop], snps)
+
+
+def _cc_stream(X, group, strat, S, fisher, device, snp_batch, verbose, stats):
+    """The streamed case/control pass: pg_cc_setup_dev once, then SNP batches from the feed (_feed._Feed) — records as they are, an array
+    batch through pg_cc_pack_x_dev into one record buffer — through pg_cc_count_dev into windows of the (p, 8) count and (p, 4) CMH
+    arrays on the device, then pg_cc_stats_dev on all p rows.  Returns the host arrays (counts, cmh, stat, hard)."""
+    L, K, t0 = _lib.load(), _lib.load_cc(), time.time()
+    src = _describe(X)
+    n, p = src.n, src.p
+    _gpus()
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
+        ldb = 0 if src.packed else -(-((n + 3) // 4) // 16) * 16           # the records of an array batch: rows on 16 bytes
+        work_bytes = int(K.pg_cc_work_bytes(n, S))
+        pb = _fit_batch(ctx, snp_batch, _lm_batch(src), p, 128, lambda pb: 185 * p + 5 * n + work_bytes + 2 * pb * src.row_bytes + pb * ldb,
+                        f"case_control: n={n}, p={p}", "185 p bytes of results, the group masks, two batch slots, the records of an array batch")
+        work, dgroup = ctx.alloc(work_bytes), ctx.to_device(group)
+        dstrat = None if strat is None else ctx.to_device(strat)
+        _lib.check(K.pg_cc_setup_dev(ctx.handle, n, S, dgroup.ptr, None if dstrat is None else dstrat.ptr, work.ptr), "pg_cc_setup_dev")
+        dc, dcmh, dst = ctx.alloc(64 * p), ctx.alloc(32 * p), ctx.alloc(8 * len(_CC_STAT) * p)
+        if not src.packed:
+            drec, dhard = ctx.alloc(pb * ldb), ctx.alloc(p)
+        for s, e, slot in feed.batches(pb):
+            out = (dc.ptr + 64 * s, dcmh.ptr + 32 * s)
+            if src.packed:
+                _call_dev(K, "pg_cc_count_dev", src, (ctx.handle, n, e - s), slot, e - s, (S, work.ptr, None, *out))
+            else:
+                _call_dev(K, "pg_cc_pack_{}_dev", src, (ctx.handle, n, e - s), slot, e - s, (drec.ptr, ldb, dhard.ptr + s))
+                _lib.check(K.pg_cc_count_dev(ctx.handle, n, e - s, drec.ptr, ldb, 0, S, work.ptr, dhard.ptr + s, *out), "pg_cc_count_dev")
+            _log(verbose - 1, f"case_control: SNPs [{s},{e}) queued")
+        _lib.check(K.pg_cc_stats_dev(ctx.handle, p, dc.ptr, dcmh.ptr, int(fisher), dst.ptr), "pg_cc_stats_dev")
+        ctx.sync()
+        hard = np.ones(p, np.bool_) if src.packed else dhard.download((p,), np.uint8).astype(np.bool_)
+        res = dc.download((p, 8), np.int64), dcmh.download((p, 4), np.float64), dst.download((p, len(_CC_STAT)), np.float64), hard
+    _stream_stats(stats, src, pb, t0)
+    _log(verbose, f"Case/control tests: {p} SNPs with {n} individuals, {S} strata in {time.time() - t0:.3f} s")
+    return res
 
 
 # ---- KING-robust relatedness and sample QC (csrc/king.hip, DESIGN §4.13) -------------------------------------------------------------------
