@@ -23,6 +23,10 @@ CC_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpygemma_cc.so")     # 
 CC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pygemma_cc.h")
 CC_SYMBOLS = []  # the functions CC_HEADER declares, in its order: filled by load_cc()
 _cc = None
+PERM_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpygemma_perm.so")     # the permutation unit: a library of its own
+PERM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pygemma_perm.h")
+PERM_SYMBOLS = []  # the functions PERM_HEADER declares, in its order: filled by load_perm()
+_perm = None
 SYMBOLS = []     # the functions HEADER declares, in its order: filled by load()
 _CTYPES = {"int": C.c_int, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
 
@@ -125,6 +129,27 @@ def load_cc():
     CC_SYMBOLS[:] = [fn for fn, _, _ in decls]
     _cc = K
     return K
+
+
+def load_perm():
+    """Load libpygemma_perm.so (csrc/perm.hip: lmm.case_control_perm's kernels) beside the main library, which it needs, and bind
+    it from include/pygemma_perm.h.  Called by lmm.case_control_perm, not at import, as load_vc is."""
+    global _perm
+    if _perm is not None:
+        return _perm
+    load()
+    for path in (PERM_LIB_PATH, PERM_HEADER):
+        if not os.path.exists(path):
+            raise PgError(f"{path} not found: build the HIP extension (python -c 'import __graft_entry__ as g; g.build()')")
+    P = C.CDLL(PERM_LIB_PATH)
+    with open(PERM_HEADER) as hdr:
+        decls = parse_header(hdr.read())
+    for fn, restype, argtypes in decls:
+        f = getattr(P, fn)
+        f.restype, f.argtypes = restype, argtypes
+    PERM_SYMBOLS[:] = [fn for fn, _, _ in decls]
+    _perm = P
+    return P
 
 
 def check(rc, what=""):

@@ -43,7 +43,7 @@ from . import model as _model
 from .vc import RemlResult, reml, vc_kinship     # noqa: F401  (re-exported: variance components for several kinship matrices)
 
 __all__ = ["pygemma", "pygemma_multi", "pygemma_score", "pygemma_gxe", "pygemma_lm", "snp_stats", "snp_filter", "SampleIter", "pinned_empty", "pin",
-           "kinship", "ld", "ld_window", "ld_prune", "clump", "ld_scores", "ldsc", "LdscResult", "epistasis", "EpistasisResult", "case_control", "prs", "prs_weights", "king", "ibs",
+           "kinship", "ld", "ld_window", "ld_prune", "clump", "ld_scores", "ldsc", "LdscResult", "epistasis", "EpistasisResult", "case_control", "case_control_perm", "PermResult", "prs", "prs_weights", "king", "ibs",
            "sample_stats", "related_pairs", "unrelated", "pca", "pca_project", "PcaResult", "reml", "vc_kinship", "RemlResult"] + _model.__all__
 
 _BATCH_BYTES = 6 << 30   # device bytes for one SNP batch of one worker (raw block, rotated block, fp16 planes)
@@ -1573,6 +1573,160 @@ def _cc_stream(X, group, strat, S, fisher, device, snp_batch, verbose, stats):
     _stream_stats(stats, src, pb, t0)
     _log(verbose, f"Case/control tests: {p} SNPs with {n} individuals, {S} strata in {time.time() - t0:.3f} s")
     return res
+
+
+# ---- max(T) permutation tests of a case/control trait (csrc/perm.hip) ----------------------------------------------------------
+_PERM_TESTS = {"allelic": 0, "trend": 1}     # PG_PERM_ALLELIC, PG_PERM_TREND
+_PERM_COLS = ("hard", "chi2", "p", "n_ge", "emp1", "emp2")
+
+
+def _perm_study(group, strat):
+    """The study flag of every sample: it has a status and (with strata) a stratum."""
+    return (group >= 0) if strat is None else ((group >= 0) & (strat >= 0))
+
+
+def _perm_labels(group, strat, S, nperm, seed):
+    """(nperm, n) int8 labellings: row b shuffles the case labels of the study samples within each of the S strata (all of them one
+    stratum without `strat`), so it keeps every stratum's number of cases and labels no excluded sample.  Row b is a function of
+    (seed, b, group, strat) alone — its own generator np.random.default_rng((seed, b)) — whatever nperm is."""
+    study = _perm_study(group, strat)
+    members = [np.flatnonzero(study & ((strat == k) if strat is not None else True)) for k in range(S)]
+    ncase = [int((group[idx] == 1).sum()) for idx in members]
+    out = np.zeros((nperm, group.shape[0]), np.int8)
+    for b in range(nperm):
+        rng = np.random.default_rng((int(seed), b))
+        for idx, r in zip(members, ncase):           # in stratum order: part of the definition of row b
+            out[b, idx[rng.permutation(idx.size)[:r]]] = 1
+    return out
+
+
+def _perm_emp2(max_null, chi2):
+    """(#{b: max_null[b] >= chi2} + 1) / (nperm + 1) per SNP; NaN where chi2 is."""
+    srt = np.sort(np.asarray(max_null, np.float64))
+    chi2 = np.asarray(chi2, np.float64)
+    bad = np.isnan(chi2)
+    ge = srt.size - np.searchsorted(srt, np.where(bad, 0.0, chi2), side="left")
+    return np.where(bad, np.nan, (ge + 1.0) / (srt.size + 1.0))
+
+
+class PermResult:
+    """What case_control_perm returns: .snps (a row per SNP: hard, chi2, p, n_ge, emp1, emp2, and SNPs when given), .max_null (nperm,)
+    the largest statistic over the SNPs under every labelling, .test, .nperm, and threshold(alpha)."""
+
+    def __init__(self, snps, max_null, test):
+        self.snps, self.max_null, self.test, self.nperm = snps, max_null, test, int(max_null.shape[0])
+
+    def threshold(self, alpha=0.05):
+        """The family-wise critical chi2 at level alpha: the ceil((1 - alpha)(nperm + 1))-th smallest of max_null (a SNP whose chi2
+        exceeds it has emp2 <= alpha); inf when that rank exceeds nperm, that is when nperm is too small for alpha.  The rank is taken
+        1e-9 below the product, so that (1 - 0.05) * 20 is the rank 19 it stands for."""
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not 0 < alpha < 1:
+            raise ValueError(f"alpha must lie in (0, 1), not {alpha!r}")
+        rank = max(1, math.ceil((1.0 - alpha) * (self.nperm + 1) - 1e-9))
+        return float("inf") if rank > self.nperm else float(np.sort(self.max_null)[rank - 1])
+
+
+def _perm_check_labels(labels, n, study):
+    labels = np.asarray(labels)
+    if labels.ndim != 2 or labels.shape[1] != n or labels.shape[0] < 1:
+        raise ValueError(f"shape mismatch: labels has shape {labels.shape}, not (nperm >= 1, {n})")
+    if labels.dtype.kind not in "biuf" or not ((labels == 0) | (labels == 1)).all():
+        raise ValueError("labels must hold 0 and 1 and nothing else")
+    if (labels[:, ~study] != 0).any():
+        raise ValueError("labels names a case among the samples that are out of the study (no status, or no stratum)")
+    return labels.astype(np.int8)
+
+
+def case_control_perm(X, y, *, nperm=1000, test="allelic", strata=None, seed=0, labels=None, snps=None, device=0, snp_batch=None, verbose=0,
+                      stats=None):
+    """max(T) permutation tests of a case/control trait: PLINK's --assoc --mperm nperm (test="allelic") and --model trend --mperm nperm
+    (test="trend"), on the int8 matrix pipe (csrc/perm.hip).  The case labels are shuffled nperm times, every SNP's statistic is
+    recomputed under every labelling from exact integer sums, and only a count per SNP and a maximum per labelling leave the device.
+
+    X (n, p) as for `ld`: hard calls only, a SNP with another observed value counts as all missing and has NaN statistics.  y (n,):
+    1 case, 0 control (bool allowed), NaN excluded.  strata: as for case_control; the shuffles stay within each stratum (PLINK's
+    --within) and a sample without a stratum is out of the study; the statistic stays the pooled one.  `labels`: an explicit
+    (nperm, n) 0/1 matrix of labellings in place of the generator's (then `nperm` and `seed` are not read); it must be 0 where a
+    sample is out of the study.  The generator's row b depends on (seed, b, y, strata) alone.
+    The frame .snps of the PermResult has p rows:
+      hard     the SNP is hard-call
+      chi2, p  the observed statistic — bit-equal to case_control's chi2_allelic / chi2_trend — and its asymptotic p on 1 df
+      n_ge     labellings whose statistic is >= chi2 (exact ties count: the sums are integers); a NaN on either side never counts
+      emp1     (n_ge + 1) / (nperm + 1), the pointwise empirical p (PLINK's EMP1)
+      emp2     (#{b: max_null[b] >= chi2} + 1) / (nperm + 1), the family-wise empirical p (EMP2)
+      SNPs     `snps`, when given
+    emp1 and emp2 are NaN where chi2 is.  .max_null[b] is the largest defined statistic over all SNPs under labelling b (0 when none
+    is defined), .threshold(alpha) the family-wise critical chi2.  The labellings are uploaded once, the SNPs streamed once in batches
+    of `snp_batch` through the two-slot feed; the result does not depend on the batch boundaries or the source kind.
+    `stats` receives batches, bytes_in, seconds.  Refused with ValueError before any device work: what case_control refuses for X, y,
+    strata, snps and snp_batch; nperm < 1; an unknown test; labels of another shape, with other values or naming an excluded sample;
+    a negative seed."""
+    _check_snp_batch(snp_batch)
+    if test not in _PERM_TESTS:
+        raise ValueError(f"test must be one of {sorted(_PERM_TESTS)}, not {test!r}")
+    X = _ld_source(X, "case_control_perm")
+    n, p = X.shape
+    if snps is not None and len(snps) != p:
+        raise ValueError(f"shape mismatch: {len(snps)} SNP names for {p} SNPs")
+    group = _epi_group(y, n, False)
+    strat, S = _cc_strata(strata, n)
+    study = _perm_study(group, strat)
+    if labels is not None:
+        lab = _perm_check_labels(labels, n, study)
+    else:
+        if isinstance(nperm, bool) or not isinstance(nperm, (int, np.integer)) or nperm < 1:
+            raise ValueError(f"nperm must be a positive integer, not {nperm!r}")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+            raise ValueError(f"seed must be a non-negative integer, not {seed!r}")
+        lab = _perm_labels(group, strat, S, int(nperm), seed)
+    nperm = lab.shape[0]
+    ldk = -(-n // 128) * 128
+    rows = np.zeros((2 + nperm, ldk), np.int8)       # the label image: the study flags, the observed status, the labellings
+    rows[0, :n] = study
+    rows[1, :n] = study & (group == 1)
+    rows[2:, :n] = lab
+    tot, obs, nge, mx, pb, src, t0 = _perm_stream(X, rows, nperm, _PERM_TESTS[test], device, snp_batch, verbose)
+    bad = np.isnan(obs)
+    out = {"hard": (tot[:, 3] & 2) == 0, "chi2": obs, "p": _cc_p1(obs), "n_ge": nge.astype(np.int64),
+           "emp1": np.where(bad, np.nan, (nge + 1.0) / (nperm + 1.0)), "emp2": _perm_emp2(mx, obs)}
+    _stream_stats(stats, src, pb, t0)
+    return PermResult(_frame(out, _PERM_COLS, snps), mx, test)
+
+
+def _perm_stream(X, rows, nperm, test, device, snp_batch, verbose):
+    """The streamed permutation pass: the label image up once and pg_perm_label_counts_dev on it, then SNP batches from the feed
+    (_feed._Feed) through pg_ld_encode_*_dev into one LD image of a batch, pg_perm_totals_dev, pg_perm_block_dev on the observed row
+    (dense: the observed statistics) and on all labellings (n_ge, max_null); one download at the end.  Returns the host arrays
+    (totals (p, 4) int32, obs, n_ge, max_null) and (pb, src, t0) for the stream's statistics."""
+    t0 = time.time()
+    src = _describe(X)
+    n, p = src.n, src.p
+    L, P = _lib.load(), _lib.load_perm()
+    _gpus()
+    nrows = rows.shape[0]
+    with _lib.Context(device) as ctx, contextlib.closing(_Feed(ctx, src)) as feed:
+        lab_bytes = int(P.pg_perm_label_bytes(n, nrows))
+        pb = _fit_batch(ctx, snp_batch, min(_LD_BATCH, _lm_batch(src)), p, 128,
+                        lambda pb: lab_bytes + 4 * nrows + 8 * nperm + 28 * p + int(L.pg_ld_image_bytes(n, pb)) + 2 * pb * src.row_bytes,
+                        f"case_control_perm: n={n}, p={p}, nperm={nperm}", "the labellings n bytes each, 28 p bytes of results, an int8 image of a batch, two batch slots")
+        dlab, dlabc = ctx.alloc(lab_bytes).upload(rows), ctx.alloc(4 * nrows)
+        _lib.check(P.pg_perm_label_counts_dev(ctx.handle, n, dlab.ptr, nrows, dlabc.ptr), "pg_perm_label_counts_dev")
+        image = ctx.alloc(L.pg_ld_image_bytes(n, pb))
+        dtot, dobs, dnge, dmax = ctx.alloc(16 * p), ctx.alloc(8 * p), ctx.alloc(4 * p), ctx.alloc(8 * nperm)
+        for buf in (dnge, dmax):
+            _lib.check(L.pg_memset(ctx.handle, buf.ptr, 0, buf.nbytes), "pg_memset")
+        for s, e, slot in feed.batches(pb):
+            _call_dev(L, "pg_ld_encode_{}_dev", src, (ctx.handle, n, e - s), slot, e - s, (image.ptr, pb, 0))
+            _lib.check(P.pg_perm_totals_dev(ctx.handle, n, image.ptr, pb, 0, e - s, dlab.ptr, dtot.ptr + 16 * s), "pg_perm_totals_dev")
+            head = (ctx.handle, n, image.ptr, pb, 0, e - s, dtot.ptr + 16 * s, dlab.ptr, dlabc.ptr)
+            _lib.check(P.pg_perm_block_dev(*head, 1, 1, test, dobs.ptr + 8 * s, 1, None, None, None), "pg_perm_block_dev")
+            _lib.check(P.pg_perm_block_dev(*head, 2, nperm, test, None, 0, dobs.ptr + 8 * s, dnge.ptr + 4 * s, dmax.ptr), "pg_perm_block_dev")
+            _log(verbose - 1, f"case_control_perm: SNPs [{s},{e}) queued")
+        ctx.sync()
+        res = (dtot.download((p, 4), np.int32), dobs.download((p,), np.float64), dnge.download((p,), np.uint32),
+               dmax.download((nperm,), np.uint64).view(np.float64))
+    _log(verbose, f"Permutation tests: {p} SNPs x {nperm} labellings with {n} individuals in {time.time() - t0:.3f} s")
+    return res + (pb, src, t0)
 
 
 # ---- KING-robust relatedness and sample QC (csrc/king.hip) -------------------------------------------------------------------
